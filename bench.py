@@ -22,10 +22,18 @@ iteration t's loss, its optimizer launch, gated on the device, after: the device
 read-back (`one_call_run_ahead`: identical results, the loss EMA is evaluated every 10, the queue drains at every window).
 
 Timed region: each loop runs on a fresh state fast-forwarded (untimed) to iteration 200 of training, W warm-up iterations, then
-blocks of exactly --steps iterations, each bracketed by barrier + device synchronize on both sides, MAX over ranks of each rank's
-own interval (barrier released -> its K iterations complete on its device); the blocks cover iterations
-200 .. 1000 whatever --steps is (40 blocks at the driver's --steps 20), `value` / `ms_per_step` are the MEDIAN block.  Nothing is
-instrumented inside it: kernel durations for `roofline` come from HIP events in a separate, untimed pass over the same stretch.
+exactly --steps iterations, split into blocks of at least 20 (at most 40 blocks), each bracketed by barrier + device synchronize
+on both sides, MAX over ranks of each rank's own interval (barrier released -> its iterations complete on its device);
+`value` / `ms_per_step` are the MEDIAN block's time per iteration.  Nothing is instrumented inside it: kernel durations for
+`roofline` come from HIP events in a separate, untimed pass over the same stretch.
+
+--dump-outputs DIR: after the timed loops, what the headline loop's last timed iteration hands its caller — the loss and the
+trained parameters (every Gaussian group and the camera poses) — as DIR/<name>.npy, at most 64 MB in all (a fixed, seeded
+sample of the Gaussians when the full set is larger).  That step (iteration 200 + W + K, same view, same learning rates) is
+recomputed, untimed, from a reproducible copy of its input: the default backward adds with float atomics in no fixed order, so
+the timed run's own state drifts from run to run; the same history replayed in the deterministic-backward mode
+is bit-identical every run, and the last step then runs through the timed path as timed.  Scene, start and view order are seeded:
+the same arguments give the same inputs, so two runs or two builds can be compared output for output.
 
 Workload (BASELINE.json configs[2], "C3"): 3-view sparse scene, 196,608 Gaussians (one per pixel of three
 256x256 pointmaps), 512x512 images, joint pose + Gaussian optimisation with the per-point optimiser.
@@ -36,7 +44,7 @@ metric reduction ("weak" scaling).
 A single-process run (no launcher) measures in a child process under --attempt-seconds and is repeated once, unpinned, if it
 stalls (`supervise`); every rank keeps to the NUMA node of its GPU (MI355GS_PIN = node | compact | off, instantsplat_amd/launch.py).
 
-python bench.py [--gpus N] [--steps K] [--warmup W]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 """
 import argparse
 import ctypes
@@ -144,6 +152,44 @@ def write_full_record(full, world):
         return None
 
 
+def timed_block_sizes(steps):
+    """The contract's K steps are exactly the timed iterations of a loop, split into blocks of at least 20 iterations (a shorter
+    block would time the synchronizes around it more than the loop) and at most 40 blocks; the sizes differ by at most one and
+    the MEDIAN block's time per iteration is reported.  The split is a function of K alone."""
+    n = max(1, min(40, steps // 20))
+    return [steps // n + (1 if i < steps % n else 0) for i in range(n)]
+
+
+DUMP_LIMIT = 64 * 10 ** 6   # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, st):
+    """--dump-outputs: what the timed loop's caller holds after its last step — that step's loss and the trained parameters —
+    as <out_dir>/<name>.npy (float64 loss, float32 parameters).  Should the per-Gaussian arrays exceed DUMP_LIMIT, the same fixed,
+    seeded sample of Gaussians (sorted indices, also written) is taken from each of them."""
+    import numpy as np
+    import torch
+    g = st.gaussians
+    per_gaussian = {"xyz": g._xyz, "features_dc": g._features_dc, "features_rest": g._features_rest, "opacity": g._opacity,
+                    "scaling": g._scaling, "rotation": g._rotation}
+    arrays = {"loss": np.array([float(st.last_loss)], dtype=np.float64), "poses": g.P.detach().float().cpu().numpy()}
+    P = g._xyz.shape[0]
+    row_bytes = sum(4 * t[0].numel() for t in per_gaussian.values())
+    fixed = sum(a.nbytes for a in arrays.values()) + 128 * (len(arrays) + len(per_gaussian) + 1)   # (+ the .npy headers)
+    rows = None
+    if fixed + row_bytes * P > DUMP_LIMIT:
+        m = (DUMP_LIMIT - fixed) // (row_bytes + 8)
+        rows = torch.randperm(P, generator=torch.Generator().manual_seed(0))[:m].sort().values
+        arrays["gaussian_index"] = rows.double().numpy()
+    for k, t in per_gaussian.items():
+        t = t.detach().float().cpu()
+        arrays[k] = (t if rows is None else t[rows]).numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def supervise(args):
     """Run this file as a child (same arguments) with a time limit; a child that stalls is killed and
     the run repeated ONCE with the CPU pinning off (MI355GS_PIN=off: the scheduler may then move it away from whatever it was
@@ -208,7 +254,12 @@ def main():
                          "proves the init path and the collectives of the N > 1 line on a 1-GPU box; `multi_gpu` is then filled")
     ap.add_argument("--attempt-seconds", type=float, default=420.0,
                     help="N = 1 without a launcher: time limit of one attempt (a stalled run is killed and repeated once, unpinned); 0 = run in this process")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed loops, write what the headline loop's last timed iteration computed (loss, trained "
+                         "parameters) as DIR/<name>.npy, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- N > 1 without a launcher: become the launcher (what replaces reference scripts/run_infer.sh:22-27,104-124 — one
     # process per GPU, all started together, then waited for).  The driver starts the ranks itself with exactly this command.
@@ -406,9 +457,7 @@ def main():
         # (an RCCL barrier is a collective launch + a device synchronize: tens of microseconds on a 6 ms block at N = 8)
         return reduce_max(own), own
 
-    # the contract's K steps are one block; the blocks cover iterations PIN_ITER + W .. ~1000 whatever K is (the driver's
-    # --steps 20 gives 40 blocks of 6 ms), and the MEDIAN block is reported.  The count is a function of K alone.
-    n_blocks = 1 if emulated else max(1, min(40, -(-(1000 - PIN_ITER) // args.steps)))
+    block_sizes = [args.steps] if emulated else timed_block_sizes(args.steps)
 
     def measure(make_step):
         """One loop under the contract's protocol on a fresh, fast-forwarded state.  make_step(state) -> (step, finish, close)."""
@@ -419,16 +468,19 @@ def main():
             step()
         finish()
         blocks, own = [], []
-        for _ in range(n_blocks):
-            b, o = timed_block(step, args.steps, finish)
+        for n in block_sizes:
+            b, o = timed_block(step, n, finish)
             blocks.append(b)
             own.append(o)
         close()
         BinningPolicy.reset("exact")
-        med = sorted(blocks)[len(blocks) // 2]
-        return {"iters_per_sec": world * args.steps / med, "ms_per_step": 1e3 * med / args.steps, "timed_blocks": len(blocks),
-                "block_seconds": blocks, "timed_seconds": sum(blocks), "first_timed_iteration": PIN_ITER + args.warmup + 1,
-                "iters_per_sec_own_clock": args.steps / sorted(own)[len(own) // 2]}, st_
+        per_step = sorted(b / n for b, n in zip(blocks, block_sizes))
+        own_per_step = sorted(o / n for o, n in zip(own, block_sizes))
+        med = per_step[len(per_step) // 2]
+        return {"iters_per_sec": world / med, "ms_per_step": 1e3 * med, "timed_blocks": len(blocks), "block_iterations": block_sizes,
+                "block_seconds": blocks, "timed_seconds": sum(blocks), "timed_iteration_count": sum(block_sizes),
+                "first_timed_iteration": PIN_ITER + args.warmup + 1,
+                "iters_per_sec_own_clock": 1.0 / own_per_step[len(own_per_step) // 2]}, st_
 
     def dropin_loop(st_):      # the reference's loop on the drop-in operators, the loss as ONE fused call (a caller who edits train.py)
         return (lambda: train_iteration(st_)), (lambda: None), (lambda: None)
@@ -501,6 +553,27 @@ def main():
     late_sib, _ = measure(dropin_loop_train_py_loss_late_item)
     synced, _ = measure(one_call_synced)
     run_ahead, _ = measure(one_call_run_ahead)
+
+    # ---- --dump-outputs (untimed): the headline loop's LAST timed step, recomputed from a reproducible copy of its input.  The
+    # timed run's own state at that step is not reproducible: the default backward adds with float atomics in no fixed order, and
+    # 200 + W + K - 1 iterations of training amplify those last bits.  So the same history (fast-forward, then the headline step
+    # W + K - 1 times: same views, same learning rates) is replayed in the deterministic-backward mode, which makes
+    # the state bit-identical run to run, and the last step then runs through the headline step in the mode it was timed in.
+    if args.dump_outputs and rank == 0:
+        from instantsplat_amd.diff_gaussian_rasterization import set_deterministic
+        was_det = set_deterministic(True)
+        try:
+            st_dump = fresh_state()
+            for _ in range(args.warmup + args.steps - 1):
+                train_iteration(st_dump, fused_loss=False)
+            dev_sync()
+        finally:
+            set_deterministic(was_det)
+        train_iteration(st_dump, fused_loss=False)
+        dev_sync()
+        BinningPolicy.reset("exact")
+        dump_outputs(args.dump_outputs, st_dump)
+        del st_dump
     elapsed = headline["ms_per_step"] * 1e-3 * args.steps
     value = headline["iters_per_sec"]
     psnr_after = evaluate_psnr(st)
@@ -1043,7 +1116,7 @@ def main():
                     "the operator's blocking instance-count read-back and the loss.item() read-back (train.py:188) every iteration — both served from "
                     "pinned host words the producing kernels store into, so neither enqueues a copy nor waits for kernels queued behind the value",
             "timed_blocks": headline["timed_blocks"], "block_seconds": headline["block_seconds"], "timed_seconds": headline["timed_seconds"],
-            "timed_iterations": f"{headline['first_timed_iteration']} .. {headline['first_timed_iteration'] + n_blocks * args.steps - 1} of training "
+            "timed_iterations": f"{headline['first_timed_iteration']} .. {headline['first_timed_iteration'] + args.steps - 1} of training "
                                 f"from seed {rank} (every loop on a fresh state fast-forwarded to iteration {PIN_ITER}); no instrumentation inside",
             "loops": {"dropin_reference_loop_train_py_loss": dict(headline, what="THE HEADLINE — train.py:171-176 as written: l1_loss(image, gt), "
                                                                                "fused_ssim(image[None], gt[None]), scalar arithmetic, loss.backward(); "

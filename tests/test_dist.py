@@ -284,3 +284,70 @@ def test_compact_line_never_exceeds_the_limit_and_says_what_it_shed(tmp_path):
     assert len(line) < bench.LINE_LIMIT == 8192 and out["line_trimmed"] is True
     assert out["roofline"]["frac"] > 0 and out["cpu_baseline"]["value"] > 0 and out["value"] > 0 and out["config"]["workload"]
     assert out["multi_gpu"]["scaling_efficiency_vs_solo_rank0"] is None and "NaN" not in line
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT_, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_steps_is_the_number_of_timed_iterations():
+    """--steps K times exactly K iterations of every loop, in blocks of at least 20 (one block below 40) and at most 40 blocks."""
+    bench = _bench_module()
+    for k in (1, 3, 20, 39, 40, 41, 200, 799, 800, 801, 5000):
+        sizes = bench.timed_block_sizes(k)
+        assert sum(sizes) == k and 1 <= len(sizes) <= 40 and max(sizes) - min(sizes) <= 1, (k, sizes)
+        assert min(sizes) >= 20 or len(sizes) == 1, (k, sizes)
+    assert bench.timed_block_sizes(800) == [20] * 40 and bench.timed_block_sizes(20) == [20]
+
+
+def test_bench_dump_outputs_is_reproducible(emu_lib_path, tmp_path):
+    """`--dump-outputs DIR` writes the headline loop's last-step loss and trained parameters as float32 / float64 .npy files,
+    and two runs with the same arguments start from the same inputs: the emulated kernels give the same outputs bit for bit."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MI355GS_BENCH_CHILD")}
+    env["OMP_NUM_THREADS"] = "2"
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT_, "bench.py"), "--steps", "3", "--warmup", "1", "--pointmap", "6", "--res", "32",
+                            "--cpu-iters", "0", "--emulated-kernels", emu_lib_path, "--dump-outputs", str(d)], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out, full = _line_and_full(r.stdout)
+        assert out["steps"] == 3 and full["loops"]["dropin_reference_loop_train_py_loss"]["timed_iteration_count"] == 3
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert set(a) == {"loss", "xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation", "poses"}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a["xyz"].shape == (3 * 6 * 6, 3) and a["poses"].shape == (3, 7) and a["loss"].shape == (1,) and a["loss"][0] > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_dump_outputs_keeps_to_the_size_limit_with_a_fixed_sample(tmp_path, monkeypatch):
+    """Past the limit, every per-Gaussian array is the same seeded sample of rows (indices written too), and the files fit."""
+    import types
+    import numpy as np
+    bench = _bench_module()
+    P = 5000
+    gen = torch.Generator().manual_seed(3)
+    g = types.SimpleNamespace(_xyz=torch.randn(P, 3, generator=gen), _features_dc=torch.randn(P, 1, 3, generator=gen),
+                              _features_rest=torch.randn(P, 15, 3, generator=gen), _opacity=torch.randn(P, 1, generator=gen),
+                              _scaling=torch.randn(P, 3, generator=gen), _rotation=torch.randn(P, 4, generator=gen), P=torch.randn(3, 7, generator=gen))
+    st = types.SimpleNamespace(gaussians=g, last_loss=0.25)
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), st)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 100_000
+    idx = np.load(tmp_path / "a" / "gaussian_index.npy").astype(np.int64)
+    assert 0 < len(idx) < P and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "xyz.npy"), g._xyz.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "features_rest.npy"), g._features_rest.numpy()[idx])
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == 0.25
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
