@@ -35,6 +35,18 @@ __device__ __forceinline__ float gw(int k) {
   return w[k];
 }
 
+// A window whose five moments are bit-equal for the two images (render = gt over the whole 11x11 window: a flat, converged
+// region) has SSIM exactly 1, d(SSIM)/d(mu1) exactly 0 and d3 = -2 d2 = 2 / B.  The general formula gets 1 and 0 there only to
+// the reciprocals' ulp, and the backward's 2 x b + y c — two terms of ~1e3 / n whose sum is 0 where x = y — turns that into
+// gradient noise of ~1e-4 relative over such a region (v_rcp_f32 is not correctly rounded; tests/test_loss_kernels_gpu.py,
+// flat_quadrant).  So such windows take the exact values, and the backward returns `a` alone where the two terms cancel exactly
+// (x = y and c = -2 b) instead of an fma's rounding residual.  Windows that are zero in both images (exx = 0: an empty background)
+// are left to the formula: its d1 is exactly 0 there, and the backward's x and y factors are 0.  Every window and pixel but the
+// nonzero equal ones keeps the formula's own bits.
+__device__ __forceinline__ bool ssim_equal_window(float mu1, float mu2, float exx, float eyy, float exy) {
+  return mu1 == mu2 && exx == eyy && exx == exy && exx != 0.f;
+}
+
 __device__ __forceinline__ float ssim_rcp(float x) {
   const float r = __builtin_amdgcn_rcpf(x);
   return fmaf(fmaf(-x, r, 1.0f), r, r);
@@ -117,10 +129,13 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float* __r
       const int gx = ox + lx + half * TS;
       if (gx < W && gy < H) {
         const bool counted = gx >= crop && gx < W - crop && gy >= crop && gy < H - crop;
-        val += counted ? m[half] : 0.f;
+        const bool same = ssim_equal_window(mu1[half], mu2[half], exx[half], eyy[half], exy[half]);
+        val += counted ? (same ? 1.f : m[half]) : 0.f;
         const size_t o = (size_t)plane * H * W + (size_t)gy * W + gx;
         if (dm_dmu1) {
-          dm_dmu1[o] = counted ? d1[half] : 0.f; dm_dsigma1_sq[o] = counted ? d2[half] : 0.f; dm_dsigma12[o] = counted ? d3[half] : 0.f;
+          dm_dmu1[o] = counted ? (same ? 0.f : d1[half]) : 0.f;
+          dm_dsigma1_sq[o] = counted ? (same ? -invB[half] : d2[half]) : 0.f;
+          dm_dsigma12[o] = counted ? (same ? 2.f * invB[half] : d3[half]) : 0.f;
         }
         l1 += fabsf(s_x[ly + HALO][lx + half * TS + HALO] - s_y[ly + HALO][lx + half * TS + HALO]);
       }
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(int H, int W, float inv_n, con
     const size_t o = po + (size_t)gy * W + gx;
     const float x = px[half], y = py[half];
     float g = 0.f;
-    if (ks != 0.f) g = ks * (a[half] + 2.f * x * b[half] + y * cc[half]);
+    if (ks != 0.f) g = ks * ((x == y && cc[half] == -2.f * b[half]) ? a[half] : a[half] + 2.f * x * b[half] + y * cc[half]);   // (see ssim_equal_window)
     if (kl != 0.f) {
       const float d = x - y;
       g += kl * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
@@ -393,10 +408,11 @@ __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const 
       const float d2 = -m * invB;
       const float d3 = 2.f * Cc * invAB;
       const bool in_img = gx >= 0 && gx < W && gy >= 0 && gy < H && r < FR1;
+      const bool same = ssim_equal_window(mu1, mu2, mo[2][j], mo[3][j], mo[4][j]);
       // (the staged inputs stay readable until the barrier below: s_d aliases them, and phase C reads only s_h)
-      mo[0][j] = in_img ? d1 : 0.f; mo[1][j] = in_img ? d2 : 0.f; mo[2][j] = in_img ? d3 : 0.f;
+      mo[0][j] = in_img ? (same ? 0.f : d1) : 0.f; mo[1][j] = in_img ? (same ? -invB : d2) : 0.f; mo[2][j] = in_img ? (same ? 2.f * invB : d3) : 0.f;
       const bool in_tile = c >= HALO && c < HALO + FT && r >= HALO && r < HALO + FT;
-      val += (in_img && in_tile) ? m : 0.f;
+      val += (in_img && in_tile) ? (same ? 1.f : m) : 0.f;
     }
     // all phase-B readers of s_xy are past the barrier above, so the maps may overwrite it
 #pragma unroll
@@ -449,7 +465,8 @@ __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const 
       if (gx < W && gy < H) {
         const float x = ex[j], y = ey[j], d = x - y;
         l1 += fabsf(d);
-        const float g = ks * (out[0][j] + 2.f * x * out[1][j] + y * out[2][j]) + kl * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
+        const float gs = (d == 0.f && out[2][j] == -2.f * out[1][j]) ? out[0][j] : out[0][j] + 2.f * x * out[1][j] + y * out[2][j];   // (see ssim_equal_window)
+        const float g = ks * gs + kl * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
         dL_dimg1[po + (size_t)gy * W + gx] = g;
       }
     }
