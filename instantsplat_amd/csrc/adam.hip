@@ -100,7 +100,9 @@ __global__ __launch_bounds__(256) void k_adam_sumsq(MultiAdamArgs a, float* __re
   __syncthreads();
   if (threadIdx.x == 0) {
     const float tot = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-    if (tot > 0.f) atomicAdd(&sumsq[a.sq_out[t]], tot);
+    // every non-zero partial, NaN and inf included: one NaN chunk makes the tensor's sum NaN, and NaN > 0 is false — the
+    // reference's `grad.norm() > 0` on a gradient holding a NaN
+    if (!(tot == 0.f)) atomicAdd(&sumsq[a.sq_out[t]], tot);
   }
 }
 
@@ -119,14 +121,16 @@ __global__ __launch_bounds__(256) void k_adam_multi(MultiAdamArgs a, const float
   bool update;
   if (a.gidx[t] == -2) {
     // the whole tensor belongs to this workgroup: evaluate its gate here (any non-zero gradient element)
-    __shared__ int s_any;
-    if (threadIdx.x == 0) s_any = 0;
+    // (sum(x^2) > 0: some x * x > 0 and no x is NaN, as the reference's `grad.norm() > 0`)
+    __shared__ int s_any, s_nan;
+    if (threadIdx.x == 0) { s_any = 0; s_nan = 0; }
     __syncthreads();
-    bool nz = false;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) { const float x = a.grad[t][i]; nz = nz || x * x > 0.f; }   // what sum(x^2) > 0 tests
-    if (nz) s_any = 1;   // benign same-value race
+    bool nz = false, nan = false;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) { const float x = a.grad[t][i]; nz = nz || x * x > 0.f; nan = nan || x != x; }
+    if (nz) s_any = 1;   // benign same-value races
+    if (nan) s_nan = 1;
     __syncthreads();
-    update = s_any != 0;
+    update = s_any != 0 && s_nan == 0;
   } else {
     update = (a.gidx[t] >= 0 ? a.gate[a.gidx[t]] : sumsq[t]) > 0.f;
   }

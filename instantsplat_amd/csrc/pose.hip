@@ -102,7 +102,9 @@ __global__ __launch_bounds__(256) void k_pose_bwd(int P, const float* __restrict
     nz_op = nz_op || r.d_opacity_logit != 0.f;
   }
   pose_accumulate(a, acc, nullptr, s_red);
-  if (gate) {  // PerPointAdam's whole-tensor gate: any non-zero gradient element (benign same-value store race)
+  // PerPointAdam's whole-tensor gate: any non-zero gradient element (benign same-value store race).  A NaN counts as non-zero
+  // here; the reference's `grad.norm() > 0` does not (same as the POSED flags in preprocess.hip)
+  if (gate) {
     if (gi_xyz >= 0 && nz_xyz) gate[gi_xyz] = 1.0f;
     if (gi_rot >= 0 && nz_rot) gate[gi_rot] = 1.0f;
     if (gi_scaling >= 0 && nz_sc) gate[gi_scaling] = 1.0f;

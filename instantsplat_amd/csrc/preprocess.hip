@@ -506,6 +506,8 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
     float a[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = 0.f;
+    // whole-tensor gate flags: any element != 0.  A NaN counts as non-zero here, while the reference's `grad.norm() > 0` is false
+    // for a gradient holding a NaN (k_adam_multi and k_adam_sumsq follow the reference; these flags do not, yet)
     bool nz_xyz = false, nz_rot = false, nz_sc = false, nz_op = false;
     if (live) {
       float act[3];

@@ -14,11 +14,18 @@ from . import _lib
 from . import diff_gaussian_rasterization as dgr
 
 
+def _aligned16(t):
+    """The pose kernels read and write the [P,4] quaternion arrays as float4: a contiguous view whose storage does not start on a
+    16-byte boundary (e.g. buf[1:].view(P, 4)) is copied first."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _PoseActivations(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, rot, scaling, opacity_logit, pose):
         L = _lib.lib()
         xyz, rot, scaling, opl, pose = map(_lib.f32c, (xyz, rot, scaling, opacity_logit, pose))
+        rot = _aligned16(rot)
         dev = _lib.require_device(xyz, rot, scaling, opl, pose)
         P = xyz.shape[0]
         means = torch.empty_like(xyz)
@@ -40,6 +47,7 @@ class _PoseActivations(torch.autograd.Function):
         P = xyz.shape[0]
         z = lambda g, like: torch.zeros_like(like) if g is None else _lib.f32c(g)
         g_means, g_rot, g_scales, g_opac = z(g_means, xyz), z(g_rot, rot), z(g_scales, scales), z(g_opac, opac)
+        g_rot = _aligned16(g_rot)
         d_xyz, d_rot, d_scaling, d_opl = torch.empty_like(xyz), torch.empty_like(rot), torch.empty_like(scales), torch.empty_like(opac)
         d_pose = torch.empty(7, dtype=torch.float32, device=dev)
         scratch = torch.empty(32, dtype=torch.float32, device=dev)

@@ -196,7 +196,7 @@ def check_train_matches_cpu_oracle(dev, iters, Wm=16, W=32, fused_step=False):
                 g64 = oracle_frame_grads(params, cam, st.gt_images[cam.uid], torch.float64)
             e_dev = float((a.double() - g64[name]).norm() / g64[name].norm())
             e_ref = float((b.double() - g64[name]).norm() / g64[name].norm())
-            assert e_dev <= max(1e-4, 2.5 * e_ref), (name, "device vs fp64", e_dev, "fp32 oracle vs fp64", e_ref)
+            assert e_dev <= min(5e-4, max(1e-4, 2.5 * e_ref)), (name, "device vs fp64", e_dev, "fp32 oracle vs fp64", e_ref)
         t.grad = None
         cpu.p[name].grad = None
 
