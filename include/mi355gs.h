@@ -427,6 +427,46 @@ void mi355gs_trainer_destroy(void* trainer);
  * as left by the last mi355gs_trainer_step — for tests and diagnostics (gradient parity of the fused step). */
 const float* mi355gs_trainer_grad(void* trainer, int k);
 
+/* ----------------------------------------------------------------------------------------------
+ * Test-view pose tracking (reference render.py:99-170, `render_set_optimize`): Gaussians frozen, one 7-vector camera pose
+ * (qw,qx,qy,qz,tx,ty,tz) optimised per view by masked L1 (mask = render > 0), torch's Adam (betas 0.9/0.999, eps 1e-8,
+ * L2 weight decay 1e-4; lr 3e-3 for t, 1e-3 for the raw quaternion, cosine-annealed) and keep-best.  One iteration is the
+ * posed projection, binning and composite forward, one masked-L1 value + gradient launch, the composite backward, a
+ * pose-only projection backward (no per-Gaussian gradient is stored) and one single-workgroup finish that sums the
+ * partials, steps Adam and keeps the best pose.  No host synchronisation inside mi355gs_tracker_run.
+ *
+ *   create: raw Gaussian parameters (read only; f_dc [P,3], f_rest [P,M-1,3] or null when M == 1), the fixed image size and
+ *   instance capacity; workspace: mi355gs_tracker_workspace_bytes() bytes, owned by the caller.  The deterministic-backward
+ *   and unit-length knobs are pinned at create.  Nothing allocates.
+ *   state: caller-owned device float[MI355GS_TRACKER_STATE_FLOATS], initialised by the caller (pose and candidate = the
+ *   initial pose, moments 0, best 1e20, initial loss NaN, flag and count 0); see the offsets below.
+ *   sched: device float[num_iter][4] per iteration i (0-based): -lr_t(i)/(1-0.9^(i+1)), -lr_q(i)/(1-0.9^(i+1)),
+ *   sqrt(1-0.999^(i+1)), unused — each computed in double and rounded to float once.
+ *   run: enqueues iterations first_iter .. first_iter+n_iters-1.  pose_trace [num_iter][7] (the pose each render used),
+ *   loss_trace [num_iter] and grad_trace [num_iter][7] (d loss / d pose) are optional (null) and indexed by iteration.
+ *   Overflow: an iteration whose instance count exceeds the capacity sets the sticky flag; it and every later iteration of
+ *   that state leave pose, moments, best and candidate unchanged.  The count slot holds the largest count seen.
+ *   count: the exact instance count at `pose` (device float[7]) into *count_out (device int32), for sizing the capacity.
+ * ---------------------------------------------------------------------------------------------- */
+#define MI355GS_TRACKER_STATE_FLOATS 40
+#define MI355GS_TRACKER_POSE 0        /* [7] current pose */
+#define MI355GS_TRACKER_EXP_AVG 8     /* [7] */
+#define MI355GS_TRACKER_EXP_AVG_SQ 16 /* [7] */
+#define MI355GS_TRACKER_BEST 24       /* best loss so far */
+#define MI355GS_TRACKER_INITIAL 25    /* loss of iteration 0 */
+#define MI355GS_TRACKER_FLAG 26       /* uint32: sticky capacity-overflow flag */
+#define MI355GS_TRACKER_COUNT 27      /* uint32: largest instance count seen */
+#define MI355GS_TRACKER_CAND 32       /* [7] best pose (the pose after the step of the best iteration) */
+size_t mi355gs_tracker_workspace_bytes(int P, int W, int H, int64_t capacity);
+void* mi355gs_tracker_create(int P, int M, int W, int H, int64_t capacity, const float* xyz, const float* f_dc, const float* f_rest,
+                             const float* opacity, const float* scaling, const float* rotation, void* workspace);
+int mi355gs_tracker_count(void* tracker, void* stream, int sh_degree, const float* projmatrix, float tanfovx, float tanfovy,
+                          const float* pose, int32_t* count_out);
+int mi355gs_tracker_run(void* tracker, void* stream, int sh_degree, const float* gt_image, const float* projmatrix, float tanfovx,
+                        float tanfovy, const float* bg, const float* sched, int num_iter, int first_iter, int n_iters, float* state,
+                        float* pose_trace, float* loss_trace, float* grad_trace);
+void mi355gs_tracker_destroy(void* tracker);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,13 +253,15 @@ int mi355gs_raster_backward(void* stream_, int P, int D, int M, int W, int H, co
   hipStream_t stream = (hipStream_t)stream_;
   if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3) return MI355GS_EINVAL;
   if (!geom || !tiles || !dL_dpix || !out_color || !grad_scratch || !bg || !viewmatrix || !projmatrix || !campos) return MI355GS_EINVAL;
-  if (P > 0 && (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacities)) return MI355GS_EINVAL;
+  // pose-only (pose tracking, see GsFusedStepHooks::pose_only): no output is stored, so none is required
+  const bool outs = !(g_fused.pose_only && g_fused.posed.pose);
+  if (P > 0 && (!means3D || !radii || (outs && (!dL_dmeans3D || !dL_dmeans2D || !dL_dopacities)))) return MI355GS_EINVAL;
   const int use_shs = shs != nullptr, use_cov = cov3D_precomp != nullptr;
-  if (P > 0 && use_shs && !dL_dshs) return MI355GS_EINVAL;
+  if (P > 0 && outs && use_shs && !dL_dshs) return MI355GS_EINVAL;
   if (shs_rest && !use_shs) return MI355GS_EINVAL;
-  if (P > 0 && !use_shs && !dL_dcolors) return MI355GS_EINVAL;
-  if (P > 0 && !use_cov && (!scales || !rotations || !dL_dscales || !dL_drotations)) return MI355GS_EINVAL;
-  if (P > 0 && use_cov && !dL_dcov3D) return MI355GS_EINVAL;
+  if (P > 0 && outs && !use_shs && !dL_dcolors) return MI355GS_EINVAL;
+  if (P > 0 && !use_cov && (!scales || !rotations || (outs && (!dL_dscales || !dL_drotations)))) return MI355GS_EINVAL;
+  if (P > 0 && outs && use_cov && !dL_dcov3D) return MI355GS_EINVAL;
   if (P == 0) return MI355GS_OK;
   const uint32_t cap = clamp_capacity(capacity);
   if (cap > 0 && !binning) return MI355GS_EINVAL;

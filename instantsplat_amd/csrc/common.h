@@ -369,5 +369,9 @@ struct GsFusedStepHooks {
   unsigned long long commit_capacity = 0;
   uint32_t* commit_poison = nullptr;   // device word, sticky: set by a launch that discarded itself; later gated launches then discard themselves too
   int gate_xyz = -1, gate_rot = -1, gate_scaling = -1, gate_opacity = -1, gate_sh = -1, gate_sh_rest = -1, gate_pose = -1;
+  // Pose tracking (tracker.hip): with `posed` set, the projection backward runs its pose-only instantiation — the chain down to
+  // the 16 pose sums only; no per-Gaussian gradient, screen-space gradient or gate flag is stored, and the output pointers of
+  // mi355gs_raster_backward may be null.
+  bool pose_only = false;
 };
 extern thread_local GsFusedStepHooks g_fused;

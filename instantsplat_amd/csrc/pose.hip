@@ -41,21 +41,8 @@ __global__ __launch_bounds__(256) void k_pose_fwd(int P, const float* __restrict
 // acc -> dL/dpose (run by one thread once every workgroup's partial sums are in)
 __device__ __forceinline__ void pose_finish(const float* __restrict__ pose, const float* acc, float* __restrict__ d_pose,
                                             float* __restrict__ pose_gate) {
-  const PoseMat m = load_pose(pose);
-  const float* Rp = acc + 3;  // dL/dR, row-major: Rp[3*i+j]
-  const float r = m.qn[0], x = m.qn[1], y = m.qn[2], z = m.qn[3];
-  float gq[4];
-  gq[0] = 2.f * (z * (Rp[3] - Rp[1]) + y * (Rp[2] - Rp[6]) + x * (Rp[7] - Rp[5]));
-  gq[1] = 2.f * (y * (Rp[1] + Rp[3]) + z * (Rp[2] + Rp[6]) + r * (Rp[7] - Rp[5])) - 4.f * x * (Rp[4] + Rp[8]);
-  gq[2] = 2.f * (x * (Rp[1] + Rp[3]) + r * (Rp[2] - Rp[6]) + z * (Rp[5] + Rp[7])) - 4.f * y * (Rp[0] + Rp[8]);
-  gq[3] = 2.f * (r * (Rp[3] - Rp[1]) + x * (Rp[2] + Rp[6]) + y * (Rp[5] + Rp[7])) - 4.f * z * (Rp[0] + Rp[4]);
-  // through q_hat = q / |q|
-  const float dot = m.qn[0] * gq[0] + m.qn[1] * gq[1] + m.qn[2] * gq[2] + m.qn[3] * gq[3];
   float d[7];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) d[k] = (gq[k] - m.qn[k] * dot) * m.inv_norm + acc[12 + k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) d[4 + k] = acc[k];
+  pose_grad_from_sums(load_pose(pose), acc, d);
   bool nz = false;
 #pragma unroll
   for (int k = 0; k < 7; ++k) { d_pose[k] = d[k]; nz = nz || d[k] != 0.f; }

@@ -81,6 +81,24 @@ __device__ __forceinline__ PoseGradOut pose_backward_one(const PoseMat& m, float
   return r;
 }
 
+// the 16 pose sums (acc[0..2] = dL/dt, acc[3..11] = dL/dR row-major, acc[12..15] = dL/dq_raw via the Hamilton product)
+// -> the 7 pose gradients (q through R(q / |q|) plus the raw-quaternion term, then t)
+__device__ __forceinline__ void pose_grad_from_sums(const PoseMat& m, const float* acc, float (&d)[7]) {
+  const float* Rp = acc + 3;  // dL/dR, row-major: Rp[3*i+j]
+  const float r = m.qn[0], x = m.qn[1], y = m.qn[2], z = m.qn[3];
+  float gq[4];
+  gq[0] = 2.f * (z * (Rp[3] - Rp[1]) + y * (Rp[2] - Rp[6]) + x * (Rp[7] - Rp[5]));
+  gq[1] = 2.f * (y * (Rp[1] + Rp[3]) + z * (Rp[2] + Rp[6]) + r * (Rp[7] - Rp[5])) - 4.f * x * (Rp[4] + Rp[8]);
+  gq[2] = 2.f * (x * (Rp[1] + Rp[3]) + r * (Rp[2] - Rp[6]) + z * (Rp[5] + Rp[7])) - 4.f * y * (Rp[0] + Rp[8]);
+  gq[3] = 2.f * (r * (Rp[3] - Rp[1]) + x * (Rp[2] + Rp[6]) + y * (Rp[5] + Rp[7])) - 4.f * z * (Rp[0] + Rp[4]);
+  // through q_hat = q / |q|
+  const float dot = m.qn[0] * gq[0] + m.qn[1] * gq[1] + m.qn[2] * gq[2] + m.qn[3] * gq[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) d[k] = (gq[k] - m.qn[k] * dot) * m.inv_norm + acc[12 + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[4 + k] = acc[k];
+}
+
 // 256-thread workgroup: sum the 16 accumulators over the workgroup, then either add them to acc[16] with device float
 // atomics, or (partial != null) store them as this workgroup's row of partial[gridDim.x][16] for a later reduction — hundreds
 // of workgroups adding to the same 16 addresses serialise at the memory side (that was most of this stage's time).

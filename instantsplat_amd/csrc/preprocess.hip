@@ -293,7 +293,9 @@ __device__ __forceinline__ void sh_backward(const float* sh, float* gsh, float x
 
 // POSED: see k_preprocess_fwd; the outputs named dL_dmeans3D / dL_drots / dL_dscales / dL_dopac then receive the gradients
 // of the RAW parameters (xyz, raw quaternion, log-scale, opacity logit) and the 16 pose sums are accumulated.
-template <bool POSED, int D>
+// POSE_ONLY (with POSED; pose tracking, tracker.hip): the same chain, SH view-direction term included, down to the 16 pose sums
+// only — nothing per Gaussian is stored (no output pointer is touched) and no gate flag is raised.
+template <bool POSED, int D, bool POSE_ONLY = false>
 __global__ __launch_bounds__(256) void k_preprocess_bwd(
     int P, int M, const float* __restrict__ means3D, const float* __restrict__ shs, const float* __restrict__ shs_rest,
     const float* __restrict__ scales, const float* __restrict__ rotations, int use_shs, int use_cov_precomp, CamParams cp, const int32_t* __restrict__ radii,
@@ -462,7 +464,7 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
   }
 
   // ---- write every output row (zeros for culled Gaussians: callers get fully-defined tensors)
-  if (live) {
+  if (live && !POSE_ONLY) {
     if (!POSED) {
       dL_dmeans3D[3 * (size_t)i] = gm[0]; dL_dmeans3D[3 * (size_t)i + 1] = gm[1]; dL_dmeans3D[3 * (size_t)i + 2] = gm[2];
       dL_dopac[i] = g.g1.y;
@@ -517,20 +519,22 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(
       const PoseGradOut r = pose_backward_one(pm, means3D[3 * (size_t)i], means3D[3 * (size_t)i + 1], means3D[3 * (size_t)i + 2],
                                               *reinterpret_cast<const float4*>(rotations + 4 * (size_t)i), act, o, gm[0], gm[1], gm[2],
                                               make_float4(gq[0], gq[1], gq[2], gq[3]), gs, g.g1.y, a);
+      if (!POSE_ONLY) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        dL_dmeans3D[3 * (size_t)i + k] = r.d_xyz[k];
-        dL_dscales[3 * (size_t)i + k] = r.d_scaling[k];
-        nz_xyz = nz_xyz || r.d_xyz[k] != 0.f;
-        nz_sc = nz_sc || r.d_scaling[k] != 0.f;
+        for (int k = 0; k < 3; ++k) {
+          dL_dmeans3D[3 * (size_t)i + k] = r.d_xyz[k];
+          dL_dscales[3 * (size_t)i + k] = r.d_scaling[k];
+          nz_xyz = nz_xyz || r.d_xyz[k] != 0.f;
+          nz_sc = nz_sc || r.d_scaling[k] != 0.f;
+        }
+        *reinterpret_cast<float4*>(dL_drots + 4 * (size_t)i) = r.d_rot;
+        nz_rot = nz_rot || r.d_rot.x != 0.f || r.d_rot.y != 0.f || r.d_rot.z != 0.f || r.d_rot.w != 0.f;
+        dL_dopac[i] = r.d_opacity_logit;
+        nz_op = nz_op || r.d_opacity_logit != 0.f;
       }
-      *reinterpret_cast<float4*>(dL_drots + 4 * (size_t)i) = r.d_rot;
-      nz_rot = nz_rot || r.d_rot.x != 0.f || r.d_rot.y != 0.f || r.d_rot.z != 0.f || r.d_rot.w != 0.f;
-      dL_dopac[i] = r.d_opacity_logit;
-      nz_op = nz_op || r.d_opacity_logit != 0.f;
     }
     pose_accumulate(a, posed.acc, posed.partial, s_red);
-    if (gate) {  // PerPointAdam's whole-tensor gate: any non-zero gradient element (benign same-value store race)
+    if (!POSE_ONLY && gate) {  // PerPointAdam's whole-tensor gate: any non-zero gradient element (benign same-value store race)
       if (gi_xyz >= 0 && nz_xyz) gate[gi_xyz] = 1.0f;
       if (gi_rot >= 0 && nz_rot) gate[gi_rot] = 1.0f;
       if (gi_scaling >= 0 && nz_sc) gate[gi_scaling] = 1.0f;
@@ -580,13 +584,15 @@ int gs_launch_preprocess_bwd(hipStream_t stream, int P, int D, int M, const floa
   float* gate = posed ? g_fused.gate : nullptr;
   const int gi[4] = {posed ? g_fused.gate_xyz : -1, posed ? g_fused.gate_rot : -1, posed ? g_fused.gate_scaling : -1,
                      posed ? g_fused.gate_opacity : -1};
-#define GS_BWD(POSED, DEG)                                                                                                              \
-  hipLaunchKernelGGL((k_preprocess_bwd<POSED, DEG>), dim3((P + 255) / 256), dim3(256), 0, stream, P, M, means3D, shs, shs_rest, scales, \
+#define GS_BWD(POSED, DEG, ...)                                                                                                         \
+  hipLaunchKernelGGL((k_preprocess_bwd<POSED, DEG, ##__VA_ARGS__>), dim3((P + 255) / 256), dim3(256), 0, stream, P, M, means3D, shs, shs_rest, scales, \
                      rotations, use_shs, use_cov_precomp, cp, radii, recs, cov3Ds, clamped, grads, dL_dmeans3D, dL_dmeans2D, dL_dshs,  \
                      dL_dshs_rest, dL_dcolors, dL_dopac, dL_dscales, dL_drots, dL_dcov3D, sh_gate, sh_rest_gate, pa, gate, gi[0],     \
                      gi[1], gi[2], gi[3])
   const int deg = use_shs ? D : 0;
-  if (posed) { if (deg == 0) GS_BWD(true, 0); else if (deg == 1) GS_BWD(true, 1); else if (deg == 2) GS_BWD(true, 2); else GS_BWD(true, 3); }
+  if (posed && g_fused.pose_only) {
+    if (deg == 0) GS_BWD(true, 0, true); else if (deg == 1) GS_BWD(true, 1, true); else if (deg == 2) GS_BWD(true, 2, true); else GS_BWD(true, 3, true);
+  } else if (posed) { if (deg == 0) GS_BWD(true, 0); else if (deg == 1) GS_BWD(true, 1); else if (deg == 2) GS_BWD(true, 2); else GS_BWD(true, 3); }
   else { if (deg == 0) GS_BWD(false, 0); else if (deg == 1) GS_BWD(false, 1); else if (deg == 2) GS_BWD(false, 2); else GS_BWD(false, 3); }
 #undef GS_BWD
   return 0;

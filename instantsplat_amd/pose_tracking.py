@@ -5,14 +5,19 @@ optimised by Adam (lr 3e-3 for t, 1e-3 for q, weight_decay 1e-4, cosine annealin
 
 Only `dL/dmeans3D` and `dL/drotations` leave the rasterizer here; the fused pose kernel reduces them to the
 seven pose gradients on the device, so one tracking iteration is ~15 kernel launches instead of ~150.
+`optimize_view_pose_fused` (render_set_optimize(..., fused=True)) runs the whole loop of a view on the device instead.
 """
 from __future__ import annotations
 
+import ctypes
+import math
 import time
 from typing import List
 
 import torch
 
+from . import _lib
+from .diff_gaussian_rasterization import BinningPolicy
 from .gaussian_renderer import render
 from .pose_utils import get_tensor_from_camera
 
@@ -64,11 +69,172 @@ def optimize_view_pose(view, gaussians, pipe, background, init_pose: torch.Tenso
     return dict(pose=pose, initial_loss=initial_loss, best_loss=float(best), render=final)
 
 
-def render_set_optimize(views: List, gaussians, pipe, background, num_iter: int = 500, init_poses=None):
+# ---- the same loop on the device (csrc/tracker.hip, include/mi355gs.h mi355gs_tracker_*): one library call enqueues a whole
+# view's iterations, one read-back of the state block per view.
+
+STATE_FLOATS, S_POSE, S_EXP_AVG, S_EXP_AVG_SQ, S_BEST, S_INITIAL, S_FLAG, S_COUNT, S_CAND = 40, 0, 8, 16, 24, 25, 26, 27, 32
+_SCHEDULES = {}
+
+
+def tracking_schedule(num_iter: int, dev) -> torch.Tensor:
+    """[num_iter, 4] float32 per iteration: Adam's step size for t and for q (-lr / (1 - 0.9^step)) and sqrt(1 - 0.999^step), each
+    formed in double as torch.optim.Adam forms them and rounded to fp32 once.  The learning rates come from a real
+    CosineAnnealingLR (torch steps it in its recursive form), read at the moment optimize_view_pose's Adam step reads them."""
+    key = (int(num_iter), str(dev))
+    tab = _SCHEDULES.get(key)
+    if tab is None:
+        ps = [torch.zeros(1, requires_grad=True), torch.zeros(1, requires_grad=True)]
+        opt = torch.optim.Adam([{"params": [ps[0]], "lr": 0.003}, {"params": [ps[1]], "lr": 0.001}], betas=(0.9, 0.999), weight_decay=1e-4)
+        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=num_iter, eta_min=0.0001)
+        rows = []
+        for it in range(num_iter):
+            step = float(it + 1)
+            bc1, bc2 = 1 - 0.9 ** step, 1 - 0.999 ** step
+            lr_t, lr_q = opt.param_groups[0]["lr"], opt.param_groups[1]["lr"]
+            rows.append(((lr_t / bc1) * -1, (lr_q / bc1) * -1, bc2 ** 0.5, 0.0))
+            opt.step()   # (no gradients: only keeps the scheduler's step-order check quiet)
+            sched.step()
+        tab = _SCHEDULES[key] = torch.tensor(rows, dtype=torch.float64).float().to(dev)
+    return tab
+
+
+class FusedPoseTracker:
+    """Handle of mi355gs_tracker_*: the frozen Gaussians' raw parameters, one image size and an instance capacity."""
+
+    def __init__(self, gaussians, W: int, H: int, capacity: int):
+        g = gaussians
+        self.params = [t.detach() for t in (g._xyz, g._features_dc, g._features_rest, g._opacity, g._scaling, g._rotation)]
+        dev = _lib.require_device(*self.params)
+        P = int(self.params[0].shape[0])
+        M = 1 + int(self.params[2].shape[1]) if self.params[2].dim() == 3 else 1
+        shapes = ((P, 3), (P, 1, 3), (P, M - 1, 3), (P, 1), (P, 3), (P, 4))
+        for t, shape in zip(self.params, shapes):   # the library indexes raw pointers with these shapes
+            if t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise ValueError(f"fused pose tracking needs float32 parameters of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+        L = _lib.lib()
+        self.dev, self.P, self.M, self.W, self.H, self.capacity = dev, P, M, int(W), int(H), int(capacity)
+        nbytes = L.mi355gs_tracker_workspace_bytes(P, self.W, self.H, self.capacity)
+        if not nbytes:
+            raise ValueError("mi355gs_tracker_workspace_bytes rejected the sizes")
+        self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        self.handle = L.mi355gs_tracker_create(P, M, self.W, self.H, self.capacity, *[_lib.ptr(t) for t in self.params],
+                                               _lib.ptr(self.workspace))
+        if not self.handle:
+            raise RuntimeError("mi355gs_tracker_create failed")
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            try:
+                _lib.lib().mi355gs_tracker_destroy(ctypes.c_void_p(handle))
+            except Exception:  # interpreter shutdown
+                pass
+
+    __del__ = close
+
+    @staticmethod
+    def _camera(view, dev):
+        proj = view.projection_matrix.to(dev).float().contiguous()
+        return proj, math.tan(view.FoVx * 0.5), math.tan(view.FoVy * 0.5)
+
+    def count(self, view, sh_degree: int, pose: torch.Tensor) -> int:
+        """Exact instance count of the view at `pose` (one blocking read)."""
+        proj, tx, ty = self._camera(view, self.dev)
+        pose = pose.detach().to(self.dev).float().contiguous()
+        out = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        with _lib.on_device(self.dev):
+            _lib.check(_lib.lib().mi355gs_tracker_count(ctypes.c_void_p(self.handle), _lib.stream_ptr(self.dev), int(sh_degree),
+                                                        _lib.ptr(proj), tx, ty, _lib.ptr(pose), _lib.ptr(out)), "tracker_count")
+        return int(out[0])
+
+    @staticmethod
+    def initial_state(pose: torch.Tensor) -> torch.Tensor:
+        st = torch.zeros(STATE_FLOATS, dtype=torch.float32, device=pose.device)
+        st[S_POSE:S_POSE + 7] = pose
+        st[S_CAND:S_CAND + 7] = pose
+        st[S_BEST] = 1e20
+        st[S_INITIAL] = float("nan")
+        return st
+
+    def run(self, view, background, sh_degree: int, state: torch.Tensor, num_iter: int, first_iter: int = 0, n_iters=None,
+            traces=None):
+        """Enqueues iterations first_iter .. first_iter + n_iters - 1 of a num_iter-iteration tracking run on `state`."""
+        dev = self.dev
+        n_iters = num_iter - first_iter if n_iters is None else n_iters
+        proj, tx, ty = self._camera(view, dev)
+        gt = view.original_image[0:3].to(dev).float().contiguous()
+        if tuple(gt.shape) != (3, self.H, self.W):
+            raise ValueError(f"ground-truth image of shape {tuple(gt.shape)}, the tracker renders {(3, self.H, self.W)}")
+        bg = background.to(dev).float().contiguous()
+        if bg.numel() != 3 or state.numel() != STATE_FLOATS or state.dtype != torch.float32 or state.device != dev:
+            raise ValueError("background needs 3 floats and state the tracker's device block")
+        sched = tracking_schedule(num_iter, dev)
+        pt, lt, gt_ = (None, None, None) if traces is None else traces
+        for t, n in ((pt, 7), (lt, 1), (gt_, 7)):
+            if t is not None and (t.numel() != n * num_iter or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+                raise ValueError("traces need float32 [num_iter, 7] / [num_iter] on the tracker's device")
+        self._keep = (proj, gt, bg, sched)   # alive until the enqueued work has read them (the caller synchronises per view)
+        with _lib.on_device(dev):
+            _lib.check(_lib.lib().mi355gs_tracker_run(ctypes.c_void_p(self.handle), _lib.stream_ptr(dev), int(sh_degree), _lib.ptr(gt),
+                                                      _lib.ptr(proj), tx, ty, _lib.ptr(bg), _lib.ptr(sched), int(num_iter), int(first_iter),
+                                                      int(n_iters), _lib.ptr(state), _lib.ptr(pt), _lib.ptr(lt), _lib.ptr(gt_)),
+                       "tracker_run")
+
+
+def _state_word(st: torch.Tensor, i: int) -> int:
+    return int(st[i:i + 1].view(torch.int32)[0])
+
+
+def optimize_view_pose_fused(view, gaussians, pipe, background, init_pose: torch.Tensor | None = None, num_iter: int = 500,
+                             record: bool = False, scaling_modifier: float = 1.0, capacity: int | None = None):
+    """optimize_view_pose on the device: the whole loop in one library call, one read-back of the state per view.  Same keys
+    (pose, initial_loss, best_loss, render — the last an ordinary no-grad render() at the best pose); record=True adds the
+    traces `poses` [num_iter, 7] (the pose each render used), `losses` [num_iter] and `grads` [num_iter, 7] (d loss / d pose).
+    capacity: instance capacity of the first attempt (default: the exact count at the initial pose, times
+    BinningPolicy.slack, plus BinningPolicy.pad); a run that outgrows it is repeated from the initial pose with larger buffers."""
+    if pipe.convert_SHs_python or pipe.compute_cov3D_python or scaling_modifier != 1.0:
+        raise ValueError("fused pose tracking implements the default pipeline only (SH colours and covariance in the operator, "
+                         "scaling_modifier 1)")
+    if num_iter <= 0:
+        raise ValueError("num_iter must be positive")
+    dev = gaussians.get_xyz.device
+    if init_pose is None:
+        init_pose = get_tensor_from_camera(view.world_view_transform.transpose(0, 1).cpu())
+    pose0 = init_pose.detach().to(dev).float().reshape(7).contiguous()
+    W, H, D = int(view.image_width), int(view.image_height), int(gaussians.active_sh_degree)
+    if capacity is None:
+        probe = FusedPoseTracker(gaussians, W, H, 1)
+        capacity = int(BinningPolicy.slack * probe.count(view, D, pose0)) + BinningPolicy.pad
+        probe.close()
+    reruns = 0
+    while True:
+        tracker = FusedPoseTracker(gaussians, W, H, capacity)
+        state = FusedPoseTracker.initial_state(pose0)
+        traces = None
+        if record:
+            traces = (torch.empty(num_iter, 7, device=dev), torch.empty(num_iter, device=dev), torch.empty(num_iter, 7, device=dev))
+        tracker.run(view, background, D, state, num_iter, traces=traces)
+        st = state.cpu()   # the one read-back of the view
+        tracker.close()
+        if _state_word(st, S_FLAG) == 0:
+            break
+        reruns += 1
+        capacity = max(int(BinningPolicy.slack * _state_word(st, S_COUNT)) + BinningPolicy.pad, 2 * capacity)
+    pose = st[S_CAND:S_CAND + 7].to(dev)
+    with torch.no_grad():
+        final = render(view, gaussians, pipe, background, camera_pose=pose)["render"]
+    out = dict(pose=pose, initial_loss=float(st[S_INITIAL]), best_loss=float(st[S_BEST]), render=final, reruns=reruns)
+    if record:
+        out.update(poses=traces[0], losses=traces[1], grads=traces[2])
+    return out
+
+
+def render_set_optimize(views: List, gaussians, pipe, background, num_iter: int = 500, init_poses=None, fused: bool = False):
     freeze_gaussians(gaussians)
+    track = optimize_view_pose_fused if fused else optimize_view_pose
     out = []
     for i, view in enumerate(views):
-        out.append(optimize_view_pose(view, gaussians, pipe, background, None if init_poses is None else init_poses[i], num_iter))
+        out.append(track(view, gaussians, pipe, background, None if init_poses is None else init_poses[i], num_iter))
     return out
 
 
