@@ -126,14 +126,17 @@ __device__ __forceinline__ float tracker_adam(float p, float d, float& m, float&
 // iteration i, taken at the pre-step pose, is compared with `<` against the best so far; a lower one makes the POST-step pose
 // the candidate; a NaN never wins).  The overflow gate reads the frame's instance count (tile_start[T]).
 __global__ __launch_bounds__(1024) void k_tracker_finish(const float* __restrict__ partial, int nrows, const float* __restrict__ loss_partial,
-                                                         int loss_nblocks, const uint32_t* __restrict__ count, unsigned long long capacity,
+                                                         int loss_nblocks, const uint32_t* __restrict__ count, const uint32_t* __restrict__ qmax,
+                                                         int nq, unsigned long long capacity,
                                                          const float4* __restrict__ sched, int iter, float* __restrict__ state,
                                                          float* __restrict__ pose_trace, float* __restrict__ loss_trace,
                                                          float* __restrict__ grad_trace) {
   __shared__ float s_sum[16][17];
   __shared__ float s_tot[16];
   __shared__ double s_la[16], s_lb[16];
+  __shared__ uint32_t s_blended;
   const int k = threadIdx.x & 15, g = threadIdx.x >> 4;
+  if (threadIdx.x == 0) s_blended = 0u;
   float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
   {
     int r = g;
@@ -152,6 +155,16 @@ __global__ __launch_bounds__(1024) void k_tracker_finish(const float* __restrict
   const float wsum = gs_sum_rows((v0 + v1) + (v2 + v3));
   if ((threadIdx.x & 63) < 16) s_sum[threadIdx.x >> 6][k] = wsum;
   __syncthreads();
+  // An all-masked frame (every m = 0) with binned instances: was any (pixel, Gaussian) pair blended?  The forward's per-quadrant
+  // maxima of the per-pixel contributor counts say so (a non-zero count is a blended pair).  Every thread sees the same 16 sums
+  // (m >= 0: their total is 0 iff each is), so the whole workgroup takes this branch or none.
+  bool masked_out = true;
+  for (int w = 0; w < 16; ++w) masked_out = masked_out && s_lb[w] == 0.0;
+  if (masked_out && *count > 0u) {
+    uint32_t any = 0u;
+    for (int i = threadIdx.x; i < nq; i += 1024) any |= qmax[i];
+    if (any) s_blended = 1u;
+  }
   if (threadIdx.x < 16) {
     float t = 0.f;
 #pragma unroll
@@ -171,9 +184,10 @@ __global__ __launch_bounds__(1024) void k_tracker_finish(const float* __restrict
   const uint32_t cnt = *count;
   // loss = sum(|r - gt| * m) / sum(m); the gradient's 1 / sum(m) in fp32 as autograd forms it.  An all-masked frame (sum(m) = 0):
   // autograd's dL/dimg is NaN at every pixel (0 * inf), which reaches the pose through every Gaussian the composite backward
-  // touches — and nothing when no instance was binned, where its pose gradient is exactly zero.
+  // touches — a blended one — and nothing when no pair was blended (no instance binned, or none passing the alpha test), where
+  // its pose gradient is exactly zero.
   const float loss = (float)(la / lb);
-  const float inv = lb > 0.0 ? 1.0f / (float)lb : (cnt > 0u ? __int_as_float(0x7fc00000) : 0.0f);
+  const float inv = lb > 0.0 ? 1.0f / (float)lb : (s_blended ? __int_as_float(0x7fc00000) : 0.0f);
 #pragma unroll
   for (int c = 0; c < 7; ++c) d[c] = lb > 0.0 ? d[c] * inv : inv;
   if (pose_trace)
@@ -314,7 +328,8 @@ int mi355gs_tracker_run(void* handle, void* stream_, int sh_degree, const float*
       return rc;
     GS_KRANGE("tracker_finish");
     hipLaunchKernelGGL(k_tracker_finish, dim3(1), dim3(1024), 0, stream, (const float*)t->pose_partial, rows,
-                       (const float*)t->loss_partial, l1_blocks, count, (unsigned long long)t->capacity, (const float4*)sched, it, state,
+                       (const float*)t->loss_partial, l1_blocks, count, (const uint32_t*)(t->tiles + tl.qmax), 4 * tl.T,
+                       (unsigned long long)t->capacity, (const float4*)sched, it, state,
                        pose_trace, loss_trace, grad_trace);
     GS_CHECK_LAUNCH("tracker_finish");
   }

@@ -58,8 +58,8 @@ def judge(group, label, dev, r32, r64, scale=None):
 
 
 def judge_components(group, label, d_dev, d_32, d_64, S):
-    """per pose component: |d_dev - d_64| <= min(CAP S_k, max(FLOOR S_k, 2.5 |d_32 - d_64|))"""
-    floor, cap = LIMITS[group]
+    """per pose component: |d_dev - d_64| <= min(CAP S_k, max(FLOOR S_k, 2.5 |d_32 - d_64|)); group: a key of LIMITS or (FLOOR, CAP)"""
+    floor, cap = LIMITS[group] if isinstance(group, str) else group
     d_dev, d_32 = d_dev.detach().cpu().double().reshape(7), d_32.detach().cpu().double().reshape(7)
     assert bool(torch.isfinite(d_dev).all()), (label, d_dev)
     for k in range(7):
