@@ -493,39 +493,22 @@ __device__ __forceinline__ void bitonic_sort_any(KeyPtr a, int n, int tid, int n
   }
 }
 
-// Lane exchange for the sort network without the LDS crossbar (ds_bpermute, two per 64-bit key): every partner pattern
-// of a bitonic network inside a wave is a DPP move or a gfx950 row swap.
+// Lane exchange for the sort network: every partner pattern of a bitonic network inside a row of 16 lanes is a DPP move.
 //   xor 1, 2: quad_perm          xor 4: row_shl:4 into banks 0,2 + row_shr:4 into banks 1,3      xor 8: row_ror:8
-//   xor 16 / 32: v_permlane16_swap / v_permlane32_swap of the value with itself, then pick by row / half
-//   flips (xor 2^k - 1): quad_perm [3,2,1,0], row_half_mirror, row_mirror (+ the xor-16 / xor-32 steps above)
+//   flips (xor 2^k - 1): quad_perm [3,2,1,0], row_half_mirror, row_mirror
 template <int CTRL>
 __device__ __forceinline__ uint32_t sort_dpp(uint32_t v) {
   // every lane has an in-range source for these patterns, so bound_ctrl only spares the compiler a zero-initialised `old`
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
 }
-__device__ __forceinline__ uint32_t sort_xor16(uint32_t u) {
-  const auto p = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  return (threadIdx.x & 16) ? p[0] : p[1];
-}
-__device__ __forceinline__ uint32_t sort_xor32(uint32_t u) {
-  const auto p = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return (threadIdx.x & 32) ? p[0] : p[1];
-}
-#ifndef GS_SORT_BPERMUTE
-#define GS_SORT_BPERMUTE 2   // shipped: 14.35 -> 13.55 us at C3 (profiles/r03_ab_sort_bpermute_kernel_avg.txt)
-#endif
-// A/B build switch (tools/build_variant.sh): lane exchanges of the network through the LDS crossbar (ds_bpermute_b32: no
-// VALU issue cycles, its own pipe) instead of DPP moves / row swaps
-// (0: none — rounds 1-2; 1: all exchanges; 2: only the ones that would need a v_permlane*_swap + select — lane masks 16, 31,
-// 32, 63: 12 VALU issue cycles per 32-bit word against one ds_bpermute.  Measured at C3: 0: 14.3 us, 1: 18.7 us (the network is
-// a chain of dependent stages and the crossbar's latency is not covered when every stage takes it), 2: 13.5 us)
-#ifndef GS_SORT_TWO_RUNS
-#define GS_SORT_TWO_RUNS 2   // A/B build switch: 0 = one network per tile; 1 = tiles of 1025 ... 1536 keys as two sorted runs merged by rank (sort_tile_two_runs); 2 = also 513 ... 768; 3 = also 1537 ... 2048 (no gain)
-#endif
+// The exchanges that cross a row of 16 lanes (lane masks 16, 31, 32, 63) go through the LDS crossbar instead (ds_bpermute_b32:
+// no VALU issue cycles, its own pipe): as a v_permlane*_swap + select they took 12 VALU issue cycles per 32-bit word.  Measured
+// at C3 (profiles/r03_ab_sort_bpermute_kernel_avg.txt): 14.35 -> 13.55 us against no crossbar at all, and 18.7 us with every
+// exchange on the crossbar (the network is a chain of dependent stages and the crossbar's latency was not covered when every
+// stage took it).
 template <int LM>
 __device__ __forceinline__ uint32_t lane_xchg32(uint32_t v) {
-  constexpr bool SORT_BPERMUTE = GS_SORT_BPERMUTE == 1 || (GS_SORT_BPERMUTE == 2 && LM >= 16);
-  if constexpr (SORT_BPERMUTE) return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63) ^ LM) << 2), (int)v);
+  if constexpr (LM >= 16) return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63) ^ LM) << 2), (int)v);
   else if constexpr (LM == 1) return sort_dpp<0xB1>(v);
   else if constexpr (LM == 2) return sort_dpp<0x4E>(v);
   else if constexpr (LM == 3) return sort_dpp<0x1B>(v);
@@ -535,13 +518,9 @@ __device__ __forceinline__ uint32_t lane_xchg32(uint32_t v) {
   }
   else if constexpr (LM == 7) return sort_dpp<0x141>(v);
   else if constexpr (LM == 8) return sort_dpp<0x128>(v);
-  else if constexpr (LM == 15) return sort_dpp<0x140>(v);
-  else if constexpr (LM == 16) return sort_xor16(v);
-  else if constexpr (LM == 31) return sort_xor16(sort_dpp<0x140>(v));
-  else if constexpr (LM == 32) return sort_xor32(v);
   else {
-    static_assert(LM == 63, "lane mask of a bitonic network inside a wave64");
-    return sort_xor32(sort_xor16(sort_dpp<0x140>(v)));
+    static_assert(LM == 15, "lane mask of a bitonic network inside a wave64");
+    return sort_dpp<0x140>(v);
   }
 }
 template <int LM>
@@ -740,20 +719,10 @@ __device__ __forceinline__ void sort_one_tile(int tile, const uint32_t* __restri
   if (n <= 0) return;
   if (n <= SORT_THREADS) sort_tile_regs<1>(s_keys, keys, list, s, n);
   else if (n <= SORT_THREADS * 2) sort_tile_regs<2>(s_keys, keys, list, s, n);
-#if GS_SORT_TWO_RUNS >= 2
   else if (n <= SORT_THREADS * 3) sort_tile_two_runs<2, 1>(s_keys, keys, list, s, n);
-#endif
-#if GS_SORT_TWO_RUNS >= 4
-  else if (n <= SORT_THREADS * 4) sort_tile_two_runs<2, 2>(s_keys, keys, list, s, n);
-#endif
   else if (n <= SORT_THREADS * 4) sort_tile_regs<4>(s_keys, keys, list, s, n);
-#if GS_SORT_TWO_RUNS >= 1
   else if (n <= SORT_THREADS * 5) sort_tile_two_runs<4, 1>(s_keys, keys, list, s, n);
   else if (n <= SORT_THREADS * 6) sort_tile_two_runs<4, 2>(s_keys, keys, list, s, n);
-#endif
-#if GS_SORT_TWO_RUNS >= 3
-  else if (n <= SORT_SMALL_CAP) sort_tile_two_runs<4, 4>(s_keys, keys, list, s, n);
-#endif
   else if (n <= SORT_SMALL_CAP) sort_tile_regs<8>(s_keys, keys, list, s, n);
   else if (n <= SORT_LDS_CAP) sort_long_tile(s_keys, keys, list, s, n);
   else {

@@ -172,13 +172,6 @@ struct CamParams {  // passed by value (kernarg): wave-uniform, lives in SGPRs
   int W, H, gx, gy;
 };
 
-// wave64 sum via butterfly shuffles; every lane gets the total
-__device__ __forceinline__ float gs_wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 // DPP (data-parallel primitive) lane exchange: one VALU op, no LDS traffic.
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ float gs_dpp(float v) {
@@ -218,13 +211,6 @@ __device__ __forceinline__ double gs_wave_sum_row3_f64(double v) {
 typedef float gs_v2f __attribute__((vector_size(8)));
 __device__ __forceinline__ gs_v2f gs_fma2(gs_v2f a, gs_v2f b, gs_v2f c) { return a * b + c; }  // contracted: v_pk_fma_f32
 
-// Hides a value's producer from the optimiser (no instruction is emitted): stops it from re-computing a product on
-// both sides of a DPP exchange, which costs more VALU ops than the exchange saves.
-__device__ __forceinline__ float gs_opaque(float v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
 // wave64 maximum, in every lane: four DPP steps inside the rows, then the two row swaps (no LDS crossbar)
 __device__ __forceinline__ uint32_t gs_wave_max_u32(uint32_t v) {
   auto dpp = [](uint32_t x, auto ctrl) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, decltype(ctrl)::value, 0xF, 0xF, true); };
@@ -254,16 +240,6 @@ __device__ __forceinline__ uint32_t gs_wave_scan_incl_u32(uint32_t v) {
   return v;
 }
 
-// Transposed pair step of a multi-value wave reduction: lanes whose `bit` is clear keep `a`, the others keep
-// `b`; each lane adds its exchange partner's copy of the value it keeps.  Two values in, one out, and the
-// surviving value differs per lane — so after log2 steps nine values are reduced with ~1/3 of the DPP traffic
-// of nine independent butterflies.  CTRL must pair lanes that differ in exactly that bit.
-template <int CTRL>
-__device__ __forceinline__ float gs_pair_reduce(bool bit, float a, float b) {
-  const float keep = bit ? b : a, send = bit ? a : b;
-  return keep + gs_dpp<CTRL>(send);
-}
-
 // Sum over the four 16-lane rows, lane-wise (every lane ends with the sum of the lanes l, l^16, l^32, l^48), with
 // gfx950's VALU row swaps — no LDS round trip (ds_bpermute) on the critical path.
 __device__ __forceinline__ float gs_sum_rows(float v) {
@@ -273,18 +249,6 @@ __device__ __forceinline__ float gs_sum_rows(float v) {
   const unsigned w = __float_as_uint(s);
   const auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// Transposed pair steps ACROSS rows with the same swaps: v_permlane16_swap exchanges the odd rows of its first operand
-// with the even rows of its second, so (first + second) afterwards holds a summed over each row pair in the even rows and
-// b in the odd rows — a pair step in two VALU ops, no selects.  v_permlane32_swap does the same for the wave halves.
-__device__ __forceinline__ float gs_pair_reduce_rows16(float a, float b) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float gs_pair_reduce_rows32(float a, float b) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
 // physical CU of the calling wave (measurement builds: tools/probe_composite.py)

@@ -131,10 +131,7 @@ __device__ __forceinline__ float gs_power2(float dx, float dy, float A, float C,
 // form, bit-identical images — a wave that finishes early no longer waits for its tile's slowest quadrant, 59 VGPRs keep eight
 // waves per SIMD, and neither the scheduler's atomics nor its bookkeeping in k_scan_tiles exist any more.
 // ------------------------------------------------------------------------------------------------
-#ifndef GS_FWD_GROUP
-#define GS_FWD_GROUP 2
-#endif
-constexpr int FWD_GROUP = GS_FWD_GROUP;   // hits per walk step (A/B build switch)
+constexpr int FWD_GROUP = 2;   // hits per walk step
 
 // FWD_TILES tiles per workgroup, dealt serpentine from the heaviest-first order (positions p, 2Q - 1 - p, 2Q + p, 4Q - 1 - p):
 // sixteen independent waves, four per SIMD — quadrant q of all four tiles.  A 512^2 frame is one resident round of 4096 waves,
@@ -143,10 +140,8 @@ constexpr int FWD_GROUP = GS_FWD_GROUP;   // hits per walk step (A/B build switc
 // and two middling tiles weigh about the same in every workgroup, and with 256 workgroups for 256 CUs a CU's load is one
 // workgroup's.  Measured at C3 (profiles/r03_ab_fwd_tiles_per_workgroup_kernel_avg.txt): 1 tile per workgroup 77.15 us, 2: 75.1, 4: 74.1.
 // A frame with more tiles than that runs in several rounds, which the dispatcher balances by itself, and big workgroups only
-// coarsen its grain (C4, 8160 tiles: 581 us with one tile per workgroup, 606 with four): the launcher picks FWD_TILES per frame.
-#ifndef GS_FWD_TILES
-#define GS_FWD_TILES 0   // 0: by the frame's tile count (gs_launch_composite_fwd); 1, 2, 4: forced (A/B builds)
-#endif
+// coarsen its grain (C4, 8160 tiles: 581 us with one tile per workgroup, 606 with four): the launcher picks FWD_TILES per frame
+// from its tile count (gs_launch_composite_fwd).
 // COUNT: the measurement instantiation (mi355gs_profile_work_counters, like the backward's): the same kernel also adds up, per
 // wave, its staged groups, hits, walk steps and the lanes of a hit that hold a blendable (pixel, Gaussian) pair — the inputs of
 // the forward's VALU-issue model in bench.py (counters[8 ..]).  The shipped launches use COUNT = false: no counters exist.
@@ -344,7 +339,8 @@ __global__ __launch_bounds__(256 * FWD_TILES) void k_composite_fwd(int T, int gx
 // them per pixel).  Gaussians whose box misses the wave's quadrant, or that lie behind every
 // pixel's last contributor, are skipped wave-wide.
 // ------------------------------------------------------------------------------------------------
-// One WAVE = one UNIT: segment `seg` (GS_SEG instances) of one tile's list; a workgroup is BW_UNITS independent waves (one, below).
+// One WAVE = one UNIT: segment `seg` (GS_SEG instances) of one tile's list; a workgroup is one wave — single-wave workgroups give
+// the dispatcher the finest grain (129.4 -> 128.2 us at C3 against four units per workgroup).
 // The state a back-to-front replay would carry into the segment comes from the forward's boundary record instead: T is the
 // forward's own product, and the colour behind is dL/dC . (final colour - colour accumulated in front of the boundary).
 //
@@ -353,52 +349,28 @@ __global__ __launch_bounds__(256 * FWD_TILES) void k_composite_fwd(int T, int gx
 //  * the nine moments of a Gaussian are first accumulated in registers over the lane's pixels (plain FMAs) and cross the
 //    lanes ONCE per (Gaussian, tile) instead of once per (Gaussian, quadrant) — a Gaussian touches 1.5-2 quadrants of a tile
 //    on the benchmark scenes, and round 1 paid the reduction (and nine atomics) for every one of them.  The reduction itself
-//    goes through LDS since round 3 (BW_REDUCE_LDS below: ~50 VALU issue cycles); rounds 1-2 transposed it in registers
+//    goes through LDS since round 3 (~50 VALU issue cycles); rounds 1-2 transposed it in registers
 //    (8 v_permlane*_swap at 8 cycles + 9 DPP / select ops: ~125 issue cycles, more than a quadrant's pixel math).
 constexpr uint32_t BW_XCD_RUN = 64;   // consecutive units sent to the same XCD (C3, FETCH_SIZE per launch: none 90 MB, 16: 56, 32: 50, 64: 47; time 124.6 / 122.1 / 122.0 / 122.7 us)
-#ifndef GS_BW_MFMA
-#define GS_BW_MFMA 0
-#endif
-#ifndef GS_BW_LDS
-#define GS_BW_LDS 1   // shipped: measured on MI355X at C3 124.5 -> 109.4 us against the register-transposed reduction (GS_BW_LDS=0),
-#endif                // 182 us with the cross-row half on the matrix pipe (GS_BW_MFMA=1); profiles/r03_ab_bwd_*
-constexpr bool BW_REDUCE_MFMA = GS_BW_MFMA != 0;   // A/B build switches of the reduction in replay_one (tools/build_variant.sh)
-constexpr bool BW_REDUCE_LDS = GS_BW_LDS != 0;
-// BW_REDUCE_LDS: the nine per-lane moments cross the wave through LDS: nine moment-major rows of 64 floats (pitch RED_PITCH:
+// The nine per-lane moments cross the wave through LDS: nine moment-major rows of 64 floats (pitch RED_PITCH:
 // 64 + 4, so that the 16-float quarters four neighbouring readers take start in different banks), written with nine
 // ds_write_b32 (lane = column) and read back by 36 lanes — moment = lane / 4, quarter = lane % 4 — as four ds_read_b128 each;
 // 15 adds, two quad_perm steps and lanes 0, 4, .., 32 hold the nine sums.  The LDS crossbar moves the data on its own pipe;
-// the VALU is left with the additions (~40 issue cycles instead of ~128 for the register-transposed form).
+// the VALU is left with the additions.  Measured on MI355X at C3: 124.5 -> 109.4 us against the register-transposed form,
+// 182 us with the cross-row half on the matrix pipe; profiles/r03_ab_bwd_*.
 constexpr int RED_PITCH = 68;
-// GS_BW_HALF: every 64-instance unit of the one-chunk instantiation is replayed by TWO waves that never meet: the BACK half of
-// the unit (instances 32..63) back to front from the unit's far boundary record, exactly as before, and the FRONT half
-// (instances 0..31) FRONT TO BACK from the near boundary record (= the previous unit's far record; T = 1, C = 0 for a tile's
-// first unit).  The forward already leaves both records (one per 64 instances): nothing changes on its side.  Front to back,
-// the colour behind Gaussian k is dL/dC . (C_out - C accumulated through k) — the same running scalar, walked the other way —
-// and the transmittance is the forward's own product T (1 - alpha), no division.  Twice the waves, half the length: the
-// backward of a 512^2 frame is ~1.84 resident rounds of 64-instance units whose last third runs below four waves per SIMD
-// (tools/probe_bwd.py), and the tail is as long as a unit.
-#ifndef GS_BW_HALF
-#define GS_BW_HALF 0
-#endif
-constexpr int BW_UNITS = 1;  // units (waves) per workgroup: single-wave workgroups give the dispatcher the finest grain (129.4 -> 128.2 us at C3 against 4)
 
 // CHUNKS: 64-instance chunks per unit (1, or 0 = the frame's own value from meta[2] for the longer units of big frames; the
 // one-chunk instantiation keeps 74 VGPRs / six waves per SIMD, the loop over chunks costs 15 more)
 // COUNT: the measurement instantiation (mi355gs_profile_work_counters): the same kernel also adds up, per wave, how many
 // (Gaussian, tile) steps it ran, how many quadrant bodies, and how many lanes of those bodies were valid pixels — the inputs
 // of the VALU-issue model bench.py reports next to the HBM roofline.  The shipped launches use COUNT = false: no counters exist.
-#ifdef GS_BW_MIN_WAVES
-#define GS_BW_BOUNDS __launch_bounds__(64 * BW_UNITS, GS_BW_MIN_WAVES)   // A/B build switch: force a register budget
-#else
-#define GS_BW_BOUNDS __launch_bounds__(64 * BW_UNITS)
-#endif
 // DET: the deterministic instantiation (mi355gs_tune_deterministic): the staged record carries the instance's ROW index instead of
 // the Gaussian's, and the nine sums of a step are stored to that row (every (Gaussian, tile) instance is replayed by exactly one
 // unit, once) instead of being added to the Gaussian's record with float atomics; k_det_gather then sums a Gaussian's rows in
 // the order of its tile rectangle.  Same arithmetic up to that final order of additions — which no longer depends on timing.
 template <int CHUNKS, bool COUNT = false, bool DET = false>
-__global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capacity,
+__global__ __launch_bounds__(64) void k_composite_bwd(int gx, int W, int H, uint32_t capacity,
                                                         const uint32_t* __restrict__ tile_start, const uint32_t* __restrict__ list,
                                                         const GsRec* __restrict__ recs, const float* __restrict__ bg,
                                                         const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
@@ -410,21 +382,14 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
                                                         const unsigned long long* __restrict__ hitmask, uint32_t max_chunks,
                                                         const uint32_t* __restrict__ qmax, const uint32_t* __restrict__ det_rowidx,
                                                         float* __restrict__ det_rows) {
-  static_assert(!DET || BW_REDUCE_LDS, "the deterministic instantiation is written for the LDS reduction");
-  __shared__ float4 s_rec[BW_UNITS][GS_SEG][3];   // the staged chunk, record-major, at a scalar address (see k_composite_fwd)
-  __shared__ __attribute__((aligned(16))) float s_red[BW_UNITS][BW_REDUCE_LDS ? 9 * RED_PITCH : 4];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = BW_UNITS == 1 ? 0 : (int)__builtin_amdgcn_readfirstlane((uint32_t)tid >> 6);
+  __shared__ float4 s_rec[GS_SEG][3];   // the staged chunk, record-major, at a scalar address (see k_composite_fwd)
+  __shared__ __attribute__((aligned(16))) float s_red[9 * RED_PITCH];
+  const int lane = threadIdx.x & 63;
   // Workgroup p runs on XCD p mod 8 (round-robin dispatch), each XCD behind its own L2.  Consecutive units are mostly units of
   // one tile and re-read the same 8 KiB of per-pixel state, so they should share an L2: inside every block of 8 * BW_XCD_RUN
   // launch positions the index is transposed, and units RUN b .. RUN b + RUN - 1 of the block all land on XCD b.
-  static_assert(BW_UNITS == 1, "the XCD transposition below is written for one unit per workgroup");
-  constexpr bool HALVES = GS_BW_HALF != 0 && CHUNKS == 1;
-  constexpr uint32_t PER_UNIT = HALVES ? 2u : 1u;   // launch positions per unit; the two halves of a unit are neighbours on one XCD
-  const uint32_t pos = blockIdx.x, in_block = pos % (8u * BW_XCD_RUN * PER_UNIT);
-  const uint32_t hu = pos - in_block + (in_block & 7u) * (BW_XCD_RUN * PER_UNIT) + (in_block >> 3);
-  const uint32_t unit = hu / PER_UNIT;
-  const bool fwd_dir = HALVES && (hu & 1u) == 0u;   // wave-uniform: this wave replays the unit's front half, front to back
+  const uint32_t pos = blockIdx.x, in_block = pos % (8u * BW_XCD_RUN);
+  const uint32_t unit = pos - in_block + (in_block & 7u) * BW_XCD_RUN + (in_block >> 3);
   if (unit >= min(meta[1], max_units)) return;  // wave-uniform; no workgroup barrier below
   // The one-chunk instantiation is launched when the CAPACITY cannot need longer units; a frame that overflowed its capacity
   // may still have been laid out in longer ones (k_scan_tiles decides from the true count).  Such a frame is discarded by its
@@ -445,15 +410,14 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
   const uint32_t slot = __builtin_amdgcn_readfirstlane(entry.z);
   if (slot >= max_units) return;   // (a frame that overflowed its buffers)
   float4 brec[4];
-  const uint32_t bslot = (fwd_dir && seg > 0u) ? slot - 1u : slot;   // front half: the record at the unit's NEAR boundary
 #pragma unroll
-  for (int qd = 0; qd < 4; ++qd) brec[qd] = bstate[(size_t)bslot * 256 + qd * 64 + lane];
+  for (int qd = 0; qd < 4; ++qd) brec[qd] = bstate[(size_t)slot * 256 + qd * 64 + lane];
   const int tx = (int)(where & 0xFFFFu), ty = (int)(where >> 16);
   const int tile = ty * gx + tx;
   const uint32_t start = min(tile_start[tile], capacity), end = min(tile_start[tile + 1], capacity);
   const uint32_t chunks = CHUNKS ? (uint32_t)CHUNKS : meta[2], seg_len = chunks * GS_SEG;   // instances per unit
   const uint32_t boff = seg * seg_len;  // contributor index (0-based) of this unit's first instance
-  float4 (*__restrict__ recl)[3] = s_rec[wave];
+  float4 (*__restrict__ recl)[3] = s_rec;
 
   // ---- the lane's four pixels
   const int px0 = tx * GS_TILE + (lane & 7), py0 = ty * GS_TILE + (lane >> 3);
@@ -480,8 +444,7 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
     if (!(px < W && py < H)) { Tr[qd] = 0.f; lastq[qd] = 0; g0[qd] = g1[qd] = g2[qd] = 0.f; }   // outside the image
   }
 #undef GS_PIN4
-  const uint32_t hlo = boff + ((HALVES && !fwd_dir) ? (uint32_t)GS_SEG / 2u : 0u);   // first instance this wave replays
-  if (end <= start + hlo) return;
+  if (end <= start + boff) return;
 #pragma unroll
   for (int qd = 0; qd < 4; ++qd) {
     behind[qd] = Tr[qd] * (bg0 * g0[qd] + bg1 * g1[qd] + bg2 * g2[qd]);  // dL/dC . (everything behind, background included)
@@ -489,18 +452,8 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
   }
   // the tile only needs instances [0, max over pixels of last)
   const uint32_t tile_max = min(max(max(wmaxq[0], wmaxq[1]), max(wmaxq[2], wmaxq[3])), end - start);
-  if (tile_max <= hlo) return;  // every pixel's last contributor lies in front of this segment
-  if (fwd_dir) {
-    // front to back from the near boundary: T in front of the unit, and dL/dC . (C_out - C accumulated in front of it) —
-    // everything from this unit's first instance to the background
-#pragma unroll
-    for (int qd = 0; qd < 4; ++qd) {
-      const bool first = seg == 0u;
-      const float c0 = first ? 0.f : brec[qd].y, c1 = first ? 0.f : brec[qd].z, c2 = first ? 0.f : brec[qd].w;
-      Tr[qd] = first ? 1.f : brec[qd].x;
-      behind[qd] = (oc0[qd] - c0) * g0[qd] + (oc1[qd] - c1) * g1[qd] + (oc2[qd] - c2) * g2[qd];
-    }
-  } else if (boff + seg_len < tile_max) {
+  if (tile_max <= boff) return;  // every pixel's last contributor lies in front of this segment
+  if (boff + seg_len < tile_max) {
     // not the deepest active unit of the tile: resume from the forward's record at this unit's far boundary
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) {
@@ -509,15 +462,6 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
     }
   }
 
-  typedef float v4f __attribute__((vector_size(16)));
-  [[maybe_unused]] float sel[9];   // BW_REDUCE_MFMA: the B operands "column c"
-  if constexpr (BW_REDUCE_MFMA) {
-#pragma unroll
-    for (int c = 0; c < 9; ++c) sel[c] = (lane & 15) == c ? 1.f : 0.f;
-  }
-  const bool bit0 = (lane & 1) != 0, bit1 = (lane & 2) != 0;
-  const bool out_lane = (lane & 14) == 0 || lane == 2;                 // the nine lanes that hold a finished sum
-  const int out_comp = lane == 2 ? 8 : (lane >> 4) + 4 * (lane & 1);   // ... and which of the nine it is
   unsigned long long mq[4];  // per quadrant: which of the staged chunk's records reach it
   uint32_t cb = 0;           // contributor index (0-based) of the staged chunk's first instance
   [[maybe_unused]] unsigned long long c_steps = 0, c_quads = 0, c_quads_valid = 0, c_lanes = 0, c_reduced = 0;
@@ -553,21 +497,10 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
           // dL/dC first, the "colour behind" term is ONE running scalar (behind) instead of the reference's three-channel
           // accum_rec / last_color / last_alpha recursion (same quantity: accum_rec_k = sum_{j>k} c_j alpha_j T_j / T_{k+1}).
           const float cg = a2.x * g0[qd] + a2.y * g1[qd] + a2.z * g2[qd];
-          float dL_dalpha, dchannel;
-          if (HALVES && fwd_dir) {
-            // front to back (wave-uniform branch): Tr is the transmittance in FRONT of this Gaussian already, `behind` still
-            // contains this Gaussian's own contribution — take it out, then step T forward with the forward's own product
-            dchannel = al * Tr[qd];
-            const float bk = behind[qd] - cg * dchannel;
-            dL_dalpha = Tr[qd] * cg - bk * inv_one_m;
-            behind[qd] = bk;
-            Tr[qd] = Tr[qd] * (1.f - al);
-          } else {
-            Tr[qd] = Tr[qd] * inv_one_m;                                  // transmittance in front of this Gaussian
-            dL_dalpha = Tr[qd] * cg - behind[qd] * inv_one_m;
-            dchannel = al * Tr[qd];
-            behind[qd] += cg * dchannel;
-          }
+          Tr[qd] = Tr[qd] * inv_one_m;                                  // transmittance in front of this Gaussian
+          const float dL_dalpha = Tr[qd] * cg - behind[qd] * inv_one_m;
+          const float dchannel = al * Tr[qd];
+          behind[qd] += cg * dchannel;
           // Moments of w = G * dL/dG over the Gaussian's pixels: every screen-space gradient of this Gaussian is a fixed
           // linear combination of them (coefficients = its own conic / opacity), applied once per Gaussian in
           // k_preprocess_bwd instead of once per pixel here:
@@ -586,70 +519,30 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
 #ifdef GS_PROBE
     pr_steps += 1;
 #endif
-    if constexpr (BW_REDUCE_LDS) {
-      if (any_valid) {
-        float* __restrict__ red = s_red[wave];
-        // (LDS operations of one wave execute in program order: the reads below see this step's writes, and the next step's
-        // writes come after these reads — no barrier; the fences keep the compiler from reordering across lanes' accesses)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        red[0 * RED_PITCH + lane] = m0; red[1 * RED_PITCH + lane] = m1; red[2 * RED_PITCH + lane] = m2;
-        red[3 * RED_PITCH + lane] = m3; red[4 * RED_PITCH + lane] = m4; red[5 * RED_PITCH + lane] = m5;
-        red[6 * RED_PITCH + lane] = m6; red[7 * RED_PITCH + lane] = m7; red[8 * RED_PITCH + lane] = m8;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float part = 0.f;
-        if (lane < 36) {
-          const float4* q = reinterpret_cast<const float4*>(red + (lane >> 2) * RED_PITCH + (lane & 3) * 16);
-          const float4 a = q[0], b = q[1], c = q[2], d = q[3];
-          part = (((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w))) + (((c.x + c.y) + (c.z + c.w)) + ((d.x + d.y) + (d.z + d.w)));
-        }
-        part += gs_dpp<0xB1>(part);   // quad_perm [1,0,3,2]
-        part += gs_dpp<0x4E>(part);   // quad_perm [2,3,0,1]: every lane of the quad holds the moment's sum over the wave
-        if constexpr (DET) {
-          if ((lane & 3) == 0 && lane < 36 && id < capacity) det_rows[(size_t)id * 12 + (lane >> 2)] = part;   // id: the instance's row
-        } else {
-          if ((lane & 3) == 0 && lane < 36) atomicAdd(reinterpret_cast<float*>(grads + id) + (lane >> 2), part);
-        }
+    if (any_valid) {
+      float* __restrict__ red = s_red;
+      // (LDS operations of one wave execute in program order: the reads below see this step's writes, and the next step's
+      // writes come after these reads — no barrier; the fences keep the compiler from reordering across lanes' accesses)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      red[0 * RED_PITCH + lane] = m0; red[1 * RED_PITCH + lane] = m1; red[2 * RED_PITCH + lane] = m2;
+      red[3 * RED_PITCH + lane] = m3; red[4 * RED_PITCH + lane] = m4; red[5 * RED_PITCH + lane] = m5;
+      red[6 * RED_PITCH + lane] = m6; red[7 * RED_PITCH + lane] = m7; red[8 * RED_PITCH + lane] = m8;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      float part = 0.f;
+      if (lane < 36) {
+        const float4* q = reinterpret_cast<const float4*>(red + (lane >> 2) * RED_PITCH + (lane & 3) * 16);
+        const float4 a = q[0], b = q[1], c = q[2], d = q[3];
+        part = (((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w))) + (((c.x + c.y) + (c.z + c.w)) + ((d.x + d.y) + (d.z + d.w)));
       }
-    } else if constexpr (BW_REDUCE_MFMA) {
-      if (any_valid) {
-        // EXPERIMENT: the cross-row half of the reduction on the matrix pipe.  v_mfma_f32_16x16x4_f32 computes
-        // D[i][j] += sum_k A[i][k] B[k][j] with A[i][k] in lane 16 k + i, B[k][j] in lane 16 k + j, D[4 R + t][j] in register t of
-        // lane 16 R + j: with A = a moment and B = "column c" (1 in lanes with lane % 16 == c) the four rows of 16 lanes are summed
-        // and moment c lands in column c; nine accumulating MFMAs put the nine moments side by side.  Exact fp32.
-        v4f acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m0, sel[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m1, sel[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m2, sel[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m3, sel[3], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m4, sel[4], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m5, sel[5], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m6, sel[6], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m7, sel[7], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(m8, sel[8], acc, 0, 0, 0);
-        // lane (R, c): register t holds the sum over the four rows of lanes 4 R + t (mod 16) -> add the registers, then the rows
-        const float mine = gs_sum_rows((acc[0] + acc[1]) + (acc[2] + acc[3]));
-        if (lane < 9) atomicAdd(reinterpret_cast<float*>(grads + id) + lane, mine);
+      part += gs_dpp<0xB1>(part);   // quad_perm [1,0,3,2]
+      part += gs_dpp<0x4E>(part);   // quad_perm [2,3,0,1]: every lane of the quad holds the moment's sum over the wave
+      if constexpr (DET) {
+        if ((lane & 3) == 0 && lane < 36 && id < capacity) det_rows[(size_t)id * 12 + (lane >> 2)] = part;   // id: the instance's row
+      } else {
+        if ((lane & 3) == 0 && lane < 36) atomicAdd(reinterpret_cast<float*>(grads + id) + (lane >> 2), part);
       }
-    } else if (any_valid) {
-      // Nine values x 64 lanes -> nine sums, transposed so that every step halves the number of live values:
-      // rows first (v_permlane16/32_swap pair steps, two ops per pair), then lane bits 0 and 1 inside the row (DPP
-      // quad_perm pair steps), then the four quads of the row (row_ror:4, row_ror:8) on the single survivor.
-      const float u0 = gs_pair_reduce_rows16(m0, m1), u1 = gs_pair_reduce_rows16(m2, m3);
-      const float u2 = gs_pair_reduce_rows16(m4, m5), u3 = gs_pair_reduce_rows16(m6, m7);
-      const float m8o = gs_opaque(m8);
-      const float u4 = gs_pair_reduce_rows16(m8o, m8o);
-      const float v0 = gs_pair_reduce_rows32(u0, u1);  // row r holds component r     (m0..m3)
-      const float v1 = gs_pair_reduce_rows32(u2, u3);  // row r holds component 4 + r (m4..m7)
-      const float v2 = gs_pair_reduce_rows32(u4, u4);  // every row holds component 8
-      const float y0 = gs_pair_reduce<0xB1>(bit0, v0, v1);
-      const float y1 = v2 + gs_dpp<0xB1>(v2);
-      float mine = gs_pair_reduce<0x4E>(bit1, y0, y1);
-      mine += gs_dpp<0x124>(mine);
-      mine += gs_dpp<0x128>(mine);
-      // lanes 16r and 16r+1 now hold components r and 4+r, lane 2 holds component 8
-      if (out_lane) atomicAdd(reinterpret_cast<float*>(grads + id) + out_comp, mine);
     }
   };
 
@@ -688,15 +581,10 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
         mq[qd] = chunk < max_chunks ? (hm[qd] & keep) : 0ull;
       }
     }
-    if constexpr (HALVES) {
-      const unsigned long long mine = fwd_dir ? 0x00000000ffffffffull : 0xffffffff00000000ull;   // this wave's half of the unit
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) mq[qd] &= mine;
-    }
     unsigned long long many = (mq[0] | mq[1]) | (mq[2] | mq[3]);
     if (!many) continue;
-    // the next instance of the walk: the deepest remaining one back to front, the nearest one front to back (scalar)
-    auto top = [&](unsigned long long m) { return (HALVES && fwd_dir) ? (int)__builtin_ctzll(m) : 63 - __clzll((long long)m); };
+    // the next instance of the walk: the deepest remaining one (scalar)
+    auto top = [](unsigned long long m) { return 63 - __clzll((long long)m); };
     // back-to-front walk over the union mask, unrolled by two with ping-pong record registers: the next record's LDS reads
     // (wave-uniform addresses: broadcasts) are issued before the current record's math
     auto xy = [&](int i) { const float4& r = recl[i][0]; return make_float2(r.x, r.y); };   // the walk only needs the centre
@@ -718,7 +606,7 @@ __global__ GS_BW_BOUNDS void k_composite_bwd(int gx, int W, int H, uint32_t capa
       if (!moreA) break;
     }
   }
-  GS_PROBE_STORE(4096u + (HALVES ? hu : unit), pr_t0, GS_PROBE_CLOCK(), pr_steps, pr_t1 - pr_t0, (unsigned long long)tile, (unsigned long long)seg,
+  GS_PROBE_STORE(4096u + unit, pr_t0, GS_PROBE_CLOCK(), pr_steps, pr_t1 - pr_t0, (unsigned long long)tile, (unsigned long long)seg,
                  (unsigned long long)gs_physical_cu(), (unsigned long long)blockIdx.x);
   if constexpr (COUNT) {
     if (lane == 0 && counters) {
@@ -824,14 +712,9 @@ int gs_launch_composite_fwd(hipStream_t stream, int T, int gx, int W, int H, uin
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     cus_of[dev] = cus = n;
   }
-  const int per_wg = GS_FWD_TILES ? GS_FWD_TILES : (T <= 4 * cus ? 4 : (T <= 4 * cus * 2 ? 2 : 1));
-  // GS_FWD_LDS_PAD (A/B builds): unused dynamic LDS per workgroup, which bounds how many workgroups a CU holds at once — fewer
-  // resident waves than work items, so that the dispatcher hands the lightest tiles to whichever CU frees a slot first
-#ifndef GS_FWD_LDS_PAD
-#define GS_FWD_LDS_PAD 0
-#endif
+  const int per_wg = T <= 4 * cus ? 4 : (T <= 4 * cus * 2 ? 2 : 1);
 #define GS_FWD(N, CNT, TRN)                                                                                                         \
-  hipLaunchKernelGGL((k_composite_fwd<N, CNT, TRN>), dim3((T + N - 1) / N), dim3(256 * N), GS_FWD_LDS_PAD, stream, T, gx, W, H, capacity, tile_start, list, recs, bg, \
+  hipLaunchKernelGGL((k_composite_fwd<N, CNT, TRN>), dim3((T + N - 1) / N), dim3(256 * N), 0, stream, T, gx, W, H, capacity, tile_start, list, recs, bg, \
                      out_color, final_T, n_contrib, order, seg_first, part_first, unit_tile, bstate, max_units, meta, hitmask, max_chunks, qmax, counters)
   if (!train) { if (per_wg == 4) GS_FWD(4, false, false); else if (per_wg == 2) GS_FWD(2, false, false); else GS_FWD(1, false, false); }
   else if (counters) { if (per_wg == 4) GS_FWD(4, true, true); else if (per_wg == 2) GS_FWD(2, true, true); else GS_FWD(1, true, true); }
@@ -840,7 +723,7 @@ int gs_launch_composite_fwd(hipStream_t stream, int T, int gx, int W, int H, uin
   return 0;
 }
 
-// one wave per backward unit (BW_UNITS per workgroup); the grid covers every unit the buffers can hold, waves past the
+// one wave per backward unit, one unit per workgroup; the grid covers every unit the buffers can hold, waves past the
 // frame's count exit
 int gs_launch_composite_bwd(hipStream_t stream, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start,
                             const uint32_t* list, const GsRec* recs, const float* bg, const float* final_T,
@@ -848,14 +731,12 @@ int gs_launch_composite_bwd(hipStream_t stream, int gx, int W, int H, uint32_t c
                             const uint4* unit_tile, const float4* bstate, const uint32_t* meta,
                             uint32_t max_units, bool may_loop, const unsigned long long* hitmask, uint32_t max_chunks,
                             const uint32_t* qmax, unsigned long long* counters, const uint32_t* det_rowidx, float* det_rows) {
-  // whole blocks of launch positions (see the index transposition in the kernel); with GS_BW_HALF the one-chunk instantiation
-  // takes two positions per unit
-  const uint32_t per_unit = (GS_BW_HALF != 0 && !may_loop) ? 2u : 1u;
-  const uint32_t blk = 8u * BW_XCD_RUN * per_unit;
-  const dim3 grid((max_units * per_unit + blk - 1u) / blk * blk);
+  // whole blocks of launch positions (see the index transposition in the kernel)
+  const uint32_t blk = 8u * BW_XCD_RUN;
+  const dim3 grid((max_units + blk - 1u) / blk * blk);
   // may_loop == false: a frame that fits this capacity has one-chunk units (count <= capacity), so the lean instantiation is safe
 #define GS_BWD(CH, CNT, DT)                                                                                                           \
-  hipLaunchKernelGGL((k_composite_bwd<CH, CNT, DT>), grid, dim3(64 * BW_UNITS), 0, stream, gx, W, H, capacity, tile_start, list, recs, bg, final_T,  \
+  hipLaunchKernelGGL((k_composite_bwd<CH, CNT, DT>), grid, dim3(64), 0, stream, gx, W, H, capacity, tile_start, list, recs, bg, final_T,  \
                      n_contrib, dL_dpix, grads, out_color, unit_tile, bstate, meta, max_units, counters, hitmask, max_chunks, qmax, det_rowidx, det_rows)
   if (det_rows) { if (!may_loop) GS_BWD(1, false, true); else GS_BWD(0, false, true); }
   else if (counters) { if (!may_loop) GS_BWD(1, true, false); else GS_BWD(0, true, false); }

@@ -288,17 +288,11 @@ constexpr int F_STAGE_ITERS = (FR2 * FXP + FTHREADS - 1) / FTHREADS;   // 6
 constexpr int FER = FT * FT / FTHREADS;   // output rows per thread in the last pass (2)
 // Run lengths of the column pass C and the row pass D (outputs per item).  A longer run reads fewer inputs per output (run + 10
 // for run outputs) but makes fewer items: 7 / 8 give 252 / 168 items for 512 threads, i.e. phase C runs on four of the
-// workgroup's eight waves.  Shorter runs that fill the workgroup were measured and are slower at 512^2 (A/B build switches,
-// profiles/r03_ab_ssim_run_lengths_kernel_avg.txt): C/D = 7/8 17.2 us (shipped), 4/8 17.5, 4/4 18.0, 6/4 18.9 — the second
+// workgroup's eight waves.  Shorter runs that fill the workgroup were measured and were slower at 512^2
+// (profiles/r03_ab_ssim_run_lengths_kernel_avg.txt): C/D = 7/8 17.2 us (shipped), 4/8 17.5, 4/4 18.0, 6/4 18.9 — the second
 // resident workgroup of the CU already fills the SIMDs, and the extra LDS reads per output cost more than the idle waves.
-#ifndef GS_SSIM_RUN_C
-#define GS_SSIM_RUN_C 7
-#endif
-#ifndef GS_SSIM_RUN_D
-#define GS_SSIM_RUN_D 8
-#endif
-constexpr int FCR = GS_SSIM_RUN_C, FC_GROUPS = (FR1 + FCR - 1) / FCR;   // 7 -> 6 groups x 42 columns = 252 items; 4 -> 11 x 42 = 462
-constexpr int FDR = GS_SSIM_RUN_D, FD_GROUPS = FT / FDR;                // 8 -> 4 groups x 42 rows = 168 items; 4 -> 8 x 42 = 336
+constexpr int FCR = 7, FC_GROUPS = (FR1 + FCR - 1) / FCR;   // 6 groups x 42 columns = 252 items
+constexpr int FDR = 8, FD_GROUPS = FT / FDR;                // 4 groups x 42 rows = 168 items
 static_assert(FC_GROUPS * FR1 <= FTHREADS && FD_GROUPS * FR1 <= FTHREADS && FT % FDR == 0 && FDR % 2 == 0, "one item per thread");
 
 __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,

@@ -317,22 +317,8 @@ static inline unsigned __builtin_amdgcn_readfirstlane(unsigned v) {
     if (emu::lane_in_op(buf, l)) return emu::from_bits<unsigned>(emu::ctx().waves[emu::wave_id()].val[buf][l]);
   return v;
 }
-static inline unsigned __builtin_amdgcn_readlane(unsigned v, int lane) {
-  int buf = emu::wave_exchange(emu::to_bits(v), true);
-  return emu::from_bits<unsigned>(emu::ctx().waves[emu::wave_id()].val[buf][lane & 63]);
-}
 // lane index inside the wave (what v_mbcnt_lo/hi(~0, 0) computes on hardware)
 static inline unsigned __lane_id() { return emu::lane_id(); }
-static inline unsigned __builtin_amdgcn_mbcnt_lo(unsigned mask, unsigned add) {
-  unsigned l = emu::lane_id();
-  unsigned lt = l >= 32 ? 0xffffffffu : ((1u << l) - 1u);
-  return add + __builtin_popcount(mask & lt);
-}
-static inline unsigned __builtin_amdgcn_mbcnt_hi(unsigned mask, unsigned add) {
-  unsigned l = emu::lane_id();
-  unsigned lt = l <= 32 ? 0u : ((1u << (l - 32)) - 1u);
-  return add + __builtin_popcount(mask & lt);
-}
 // v_mov_b32_dpp semantics (GFX9 DPP): returns src from the lane selected by dpp_ctrl; lanes whose
 // source is out of range, or whose row/bank is masked off, keep `old` (bound_ctrl: 0 instead).
 static inline int __builtin_amdgcn_update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
@@ -391,20 +377,6 @@ static inline emu_uint2v __builtin_amdgcn_permlane32_swap(unsigned old, unsigned
   r.v[1] = l >= 32 ? S(l) : D(l + 32);
   return r;
 }
-// v_mfma_f32_16x16x4_f32: D[i][j] = C[i][j] + sum_k A[i][k] B[k][j]; A[i][k] in lane 16 k + i, B[k][j] in lane 16 k + j,
-// D[4 R + t][j] in element t of lane 16 R + j (CDNA3/4 ISA guide, matrix layouts).  All 64 lanes must be active.
-typedef float emu_v4f __attribute__((vector_size(16)));
-static inline emu_v4f __builtin_amdgcn_mfma_f32_16x16x4f32(float a, float b, emu_v4f c, int, int, int) {
-  int buf = emu::wave_exchange(((uint64_t)emu::from_bits<unsigned>(emu::to_bits(b)) << 32) | emu::from_bits<unsigned>(emu::to_bits(a)), true);
-  auto& ws = emu::ctx().waves[emu::wave_id()];
-  auto A = [&](unsigned lane) { return emu::from_bits<float>(ws.val[buf][lane] & 0xffffffffu); };
-  auto B = [&](unsigned lane) { return emu::from_bits<float>(ws.val[buf][lane] >> 32); };
-  const unsigned l = emu::lane_id(), R = l >> 4, j = l & 15;
-  emu_v4f d = c;
-  for (unsigned t = 0; t < 4; ++t)
-    for (unsigned k = 0; k < 4; ++k) d[t] += A(16 * k + 4 * R + t) * B(16 * k + j);
-  return d;
-}
 // hardware-id registers (read by the measurement build's probes only): a made-up placement of 7 "CUs" x 2 "XCCs"
 static inline unsigned __builtin_amdgcn_s_getreg(int simm16) {
   const unsigned b = blockIdx.x;
@@ -413,9 +385,6 @@ static inline unsigned __builtin_amdgcn_s_getreg(int simm16) {
 #define __HIP_MEMORY_SCOPE_AGENT 4
 template <class T> static inline T __hip_atomic_load(const T* p, int, int) { return *p; }
 template <class T, class V> static inline void __hip_atomic_store(T* p, V v, int, int) { *p = (T)v; }
-static inline void __builtin_amdgcn_s_setprio(int) {}
-static inline void __builtin_amdgcn_s_sleep(int) {}
-static inline void __builtin_amdgcn_sched_barrier(int) {}
 static inline unsigned long long __ballot(int pred);
 static inline void __builtin_amdgcn_wave_barrier() { (void)__ballot(1); }   // the fibers of a wave meet here
 #define __builtin_amdgcn_fence(order, scope) ((void)0)

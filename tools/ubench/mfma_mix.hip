@@ -1,7 +1,7 @@
 // Micro-benchmark: do the matrix pipe and the VALU of one gfx950 SIMD overlap for the instruction mix of the backward
 // composite kernel?  A wave runs ITERS rounds of [NV plain fp32 VALU instructions, then NM dependent v_mfma_f32_16x16x4_f32
 // on one accumulator, then the accumulator read-back] — the shape of one (Gaussian, tile) step whose cross-row reduction runs
-// on the matrix pipe (composite.hip, GS_BW_MFMA build).  Reported: cycles per round per SIMD with W waves resident per SIMD,
+// on the matrix pipe (the former GS_BW_MFMA build of composite.hip, removed after it lost its A/B).  Reported: cycles per round per SIMD with W waves resident per SIMD,
 // for the VALU part alone, the MFMA part alone and both.  If the pipes overlapped perfectly "both" would equal the larger of
 // the two; if they serialised, their sum.     hipcc --offload-arch=gfx950 -O3 -o mfma_mix mfma_mix.hip
 #include <hip/hip_runtime.h>
@@ -12,7 +12,7 @@
 constexpr int ITERS = 1024;
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-// SHAPE 0: VALU block, then NM MFMAs chained on ONE accumulator (the GS_BW_MFMA build of composite.hip)
+// SHAPE 0: VALU block, then NM MFMAs chained on ONE accumulator (the former GS_BW_MFMA build of composite.hip)
 // SHAPE 1: VALU block, then NM MFMAs on NM / 3 chains of three (independent accumulators)
 // SHAPE 2: the NM MFMAs (independent accumulators) spread evenly through the VALU block
 template <int NV, int NM, int KIND, int SHAPE = 0> __global__ __launch_bounds__(64) void k(float* out, float seed, long long* cycles) {
