@@ -129,12 +129,6 @@ BINDING = os.environ.get("MI355GS_BINDING", "compiled")
 EXT_PATH = os.path.join(_HERE, "lib", "_mi355gs_torch.so")
 _EXT = None
 _EXT_BOUND_TO = None
-_EXT_SYMBOLS = ("mi355gs_raster_geom_bytes", "mi355gs_raster_tiles_bytes", "mi355gs_raster_binning_bytes",
-                "mi355gs_raster_grad_scratch_bytes", "mi355gs_raster_grad_gate_offset", "mi355gs_posed_forward_preprocess", "mi355gs_raster_forward_preprocess", "mi355gs_raster_backward",
-                "mi355gs_raster_forward_render", "mi355gs_raster_binning_bytes_render_only", "mi355gs_raster_forward_render_only", "mi355gs_posed_backward", "mi355gs_ssim_scratch_bytes", "mi355gs_l1_ssim_loss_fused", "mi355gs_ssim_forward", "mi355gs_ssim_backward",
-                "mi355gs_adam_multi_step", "mi355gs_error_string", "mi355gs_l1_scratch_bytes", "mi355gs_l1_loss_forward", "mi355gs_l1_loss_backward",
-                "mi355gs_l1_ssim_pair_forward", "mi355gs_l1_ssim_pair_backward", "mi355gs_loss_program_eval",
-                "mi355gs_loss_program_eval_grad")
 
 
 def compiled():
@@ -156,7 +150,7 @@ def compiled():
         _EXT = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(_EXT)
     _EXT.forget_gates()
-    _EXT.bind({name: ctypes.cast(getattr(L, name), ctypes.c_void_p).value for name in _EXT_SYMBOLS}, _TEST_MODE)
+    _EXT.bind({name: ctypes.cast(getattr(L, name), ctypes.c_void_p).value for name in _EXT.abi_symbols()}, _TEST_MODE)
     _EXT_BOUND_TO = L
     return _EXT
 

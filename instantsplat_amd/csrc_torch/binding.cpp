@@ -28,36 +28,49 @@ using torch::Tensor;
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
-// ---- C ABI entry points (addresses handed over by _lib.py: whichever build of the library the package has loaded)
+// ---- C ABI entry points (addresses handed over by _lib.py: whichever build of the library the package has loaded).
+// The one list of them, X(field of g_abi, C symbol): the struct's members, the names _lib.py looks up (abi_symbols) and the
+// binding loop are all generated from it.
+#define GS_ABI_LIST(X)                                                 \
+  X(geom_bytes, mi355gs_raster_geom_bytes)                             \
+  X(tiles_bytes, mi355gs_raster_tiles_bytes)                           \
+  X(binning_bytes, mi355gs_raster_binning_bytes)                       \
+  X(grad_scratch_bytes, mi355gs_raster_grad_scratch_bytes)             \
+  X(grad_gate_offset, mi355gs_raster_grad_gate_offset)                 \
+  X(posed_forward_preprocess, mi355gs_posed_forward_preprocess)        \
+  X(forward_preprocess, mi355gs_raster_forward_preprocess)             \
+  X(raster_backward, mi355gs_raster_backward)                          \
+  X(forward_render, mi355gs_raster_forward_render)                     \
+  X(binning_bytes_render_only, mi355gs_raster_binning_bytes_render_only) \
+  X(forward_render_only, mi355gs_raster_forward_render_only)           \
+  X(posed_backward, mi355gs_posed_backward)                            \
+  X(ssim_scratch_bytes, mi355gs_ssim_scratch_bytes)                    \
+  X(l1_ssim_loss_fused, mi355gs_l1_ssim_loss_fused)                    \
+  X(l1_scratch_bytes, mi355gs_l1_scratch_bytes)                        \
+  X(l1_loss_forward, mi355gs_l1_loss_forward)                          \
+  X(l1_loss_backward, mi355gs_l1_loss_backward)                        \
+  X(pair_forward, mi355gs_l1_ssim_pair_forward)                        \
+  X(pair_backward, mi355gs_l1_ssim_pair_backward)                      \
+  X(program_eval, mi355gs_loss_program_eval)                           \
+  X(program_eval_grad, mi355gs_loss_program_eval_grad)                 \
+  X(ssim_forward, mi355gs_ssim_forward)                                \
+  X(ssim_backward, mi355gs_ssim_backward)                              \
+  X(adam_multi_step, mi355gs_adam_multi_step)                          \
+  X(error_string, mi355gs_error_string)
+
 struct Abi {
-  decltype(&mi355gs_raster_geom_bytes) geom_bytes = nullptr;
-  decltype(&mi355gs_raster_tiles_bytes) tiles_bytes = nullptr;
-  decltype(&mi355gs_raster_binning_bytes) binning_bytes = nullptr;
-  decltype(&mi355gs_raster_grad_scratch_bytes) grad_scratch_bytes = nullptr;
-  decltype(&mi355gs_raster_grad_gate_offset) grad_gate_offset = nullptr;
-  decltype(&mi355gs_posed_forward_preprocess) posed_forward_preprocess = nullptr;
-  decltype(&mi355gs_raster_forward_preprocess) forward_preprocess = nullptr;
-  decltype(&mi355gs_raster_backward) raster_backward = nullptr;
-  decltype(&mi355gs_raster_forward_render) forward_render = nullptr;
-  decltype(&mi355gs_raster_binning_bytes_render_only) binning_bytes_render_only = nullptr;
-  decltype(&mi355gs_raster_forward_render_only) forward_render_only = nullptr;
-  decltype(&mi355gs_posed_backward) posed_backward = nullptr;
-  decltype(&mi355gs_ssim_scratch_bytes) ssim_scratch_bytes = nullptr;
-  decltype(&mi355gs_l1_ssim_loss_fused) l1_ssim_loss_fused = nullptr;
-  decltype(&mi355gs_l1_scratch_bytes) l1_scratch_bytes = nullptr;
-  decltype(&mi355gs_l1_loss_forward) l1_loss_forward = nullptr;
-  decltype(&mi355gs_l1_loss_backward) l1_loss_backward = nullptr;
-  decltype(&mi355gs_l1_ssim_pair_forward) pair_forward = nullptr;
-  decltype(&mi355gs_l1_ssim_pair_backward) pair_backward = nullptr;
-  decltype(&mi355gs_loss_program_eval) program_eval = nullptr;
-  decltype(&mi355gs_loss_program_eval_grad) program_eval_grad = nullptr;
-  decltype(&mi355gs_ssim_forward) ssim_forward = nullptr;
-  decltype(&mi355gs_ssim_backward) ssim_backward = nullptr;
-  decltype(&mi355gs_adam_multi_step) adam_multi_step = nullptr;
-  decltype(&mi355gs_error_string) error_string = nullptr;
+#define GS_MEMBER(field, name) decltype(&name) field = nullptr;
+  GS_ABI_LIST(GS_MEMBER)
+#undef GS_MEMBER
   bool bound = false;
   bool allow_cpu = false;   // only the CPU test tier (SIMT-emulated build of the kernels) runs on CPU tensors
 } g_abi;
+
+std::vector<std::string> abi_symbols() {
+#define GS_NAME(field, name) #name,
+  return {GS_ABI_LIST(GS_NAME)};
+#undef GS_NAME
+}
 
 void bind_abi(const std::map<std::string, uintptr_t>& sym, bool allow_cpu_tensors) {
   g_abi.allow_cpu = allow_cpu_tensors;
@@ -66,32 +79,8 @@ void bind_abi(const std::map<std::string, uintptr_t>& sym, bool allow_cpu_tensor
     TORCH_CHECK(it != sym.end() && it->second, "mi355gs torch binding: entry point ", name, " was not provided");
     return it->second;
   };
-#define GS_BIND(field, name) g_abi.field = reinterpret_cast<decltype(g_abi.field)>(get(#name))
-  GS_BIND(geom_bytes, mi355gs_raster_geom_bytes);
-  GS_BIND(tiles_bytes, mi355gs_raster_tiles_bytes);
-  GS_BIND(binning_bytes, mi355gs_raster_binning_bytes);
-  GS_BIND(grad_scratch_bytes, mi355gs_raster_grad_scratch_bytes);
-  GS_BIND(grad_gate_offset, mi355gs_raster_grad_gate_offset);
-  GS_BIND(posed_forward_preprocess, mi355gs_posed_forward_preprocess);
-  GS_BIND(forward_preprocess, mi355gs_raster_forward_preprocess);
-  GS_BIND(raster_backward, mi355gs_raster_backward);
-  GS_BIND(forward_render, mi355gs_raster_forward_render);
-  GS_BIND(binning_bytes_render_only, mi355gs_raster_binning_bytes_render_only);
-  GS_BIND(forward_render_only, mi355gs_raster_forward_render_only);
-  GS_BIND(posed_backward, mi355gs_posed_backward);
-  GS_BIND(ssim_scratch_bytes, mi355gs_ssim_scratch_bytes);
-  GS_BIND(l1_ssim_loss_fused, mi355gs_l1_ssim_loss_fused);
-  GS_BIND(l1_scratch_bytes, mi355gs_l1_scratch_bytes);
-  GS_BIND(l1_loss_forward, mi355gs_l1_loss_forward);
-  GS_BIND(l1_loss_backward, mi355gs_l1_loss_backward);
-  GS_BIND(pair_forward, mi355gs_l1_ssim_pair_forward);
-  GS_BIND(pair_backward, mi355gs_l1_ssim_pair_backward);
-  GS_BIND(program_eval, mi355gs_loss_program_eval);
-  GS_BIND(program_eval_grad, mi355gs_loss_program_eval_grad);
-  GS_BIND(ssim_forward, mi355gs_ssim_forward);
-  GS_BIND(ssim_backward, mi355gs_ssim_backward);
-  GS_BIND(adam_multi_step, mi355gs_adam_multi_step);
-  GS_BIND(error_string, mi355gs_error_string);
+#define GS_BIND(field, name) g_abi.field = reinterpret_cast<decltype(&name)>(get(#name));
+  GS_ABI_LIST(GS_BIND)
 #undef GS_BIND
   g_abi.bound = true;
 }
@@ -202,8 +191,8 @@ struct GateRecord {
 std::mutex g_gate_mutex;
 GateRecord g_gates;
 
-// Does a backward of this call exist at all?  (The forward then owns the backward's accumulator buffer already and lets the
-// projection kernel clear it on its way: no memset in front of the backward's first kernel.)
+// Does a backward of this call exist at all?  (FrameForward below takes two decisions from the answer: whether the forward
+// allocates the backward's accumulator buffer, and which form of stage 2 runs.)
 template <class... T> bool any_requires_grad(const T&... t) {
   if (!at::GradMode::is_enabled()) return false;
   bool any = false;
@@ -213,8 +202,6 @@ template <class... T> bool any_requires_grad(const T&... t) {
 // ... asked where the operator is CALLED: inside a custom function's forward() grad mode is off, so the question would always be
 // answered "no" there (round 4 shipped it that way for a while: the backward's memset stayed, profiles/r04_dropin_aten_ops.txt)
 thread_local bool t_backward_follows = false;
-bool g_render_only_when_no_grad = true;   // A/B switch (render_only): false = every forward runs the training instantiation of stage 2
-bool g_forward_owns_scratch = true;   // A/B switch (forward_owns_scratch): false = the backward allocates and memsets, as before ABI v7
 struct BackwardFollows {
   explicit BackwardFollows(bool v) { t_backward_follows = v; }
   ~BackwardFollows() { t_backward_follows = false; }
@@ -332,6 +319,92 @@ void check_frame_buffers(const Tensor& binning, const Tensor& scratch, int64_t R
 }
 
 // ------------------------------------------------------------------------------------------------
+// What the forwards of the two render nodes share: the frame's buffers, stage 2 and the decision how large to lay it out.
+// A node constructs one (count word checked, `radii` allocated), allocates what is its own, and calls run() with the one thing
+// that differs between the nodes: `project(frame)`, which enqueues the node's projection call on the frame's buffers.
+// ------------------------------------------------------------------------------------------------
+struct FrameForward {
+  Tensor radii, color, geom, tiles, binning;
+  // The backward's accumulator buffer, when a backward will follow (t_backward_follows): allocated now and cleared by the
+  // projection kernel on its way, so no memset stands in front of the backward's first kernel.  Undefined otherwise.
+  Tensor scratch;
+  int64_t R = 0;     // the capacity the frame's buffers were laid out for: the backward needs this number
+  int32_t* count;    // pinned host memory the tile-scan kernel stores into (a CPU word under emulation)
+
+  FrameForward(const Tensor& like, int P, const Tensor& count_slot) {
+    TORCH_CHECK(count_slot.scalar_type() == at::kInt && count_slot.numel() == 1, "count_slot must be one int32");
+    count = count_slot.data_ptr<int32_t>();
+    radii = at::empty({P}, like.options().dtype(at::kInt));
+  }
+
+  template <class Project>
+  void run(const DeviceScope& dev, const Tensor& like, int P, int W, int H, const Tensor& bg, int64_t capacity, int64_t count_hint,
+           const Project& project) {
+    color = at::empty({3, H, W}, like.options());
+    geom = empty_bytes(g_abi.geom_bytes(P), like);
+    tiles = empty_bytes(g_abi.tiles_bytes(W, H), like);
+    if (t_backward_follows) scratch = empty_bytes(g_abi.grad_scratch_bytes(P), like);
+    auto preprocess = [&]() {
+      *reinterpret_cast<volatile int32_t*>(count) = -1;   // "not written yet" for wait_for_count
+      project(*this);
+    };
+    // no backward will follow (nothing requires a gradient, or grad mode is off where the operator was called): the render-only
+    // stage 2 — a binning buffer of keys + lists only, no boundary records / hit masks / unit table left for a backward
+    auto stage2 = [&](int64_t cap) {
+      if (t_backward_follows) {
+        binning = empty_bytes(g_abi.binning_bytes(cap, W, H), like);
+        check(g_abi.forward_render(dev.stream, P, W, H, cap, fp(bg), geom.data_ptr(), tiles.data_ptr(), binning.data_ptr(), fp(color), 0),
+              "raster_forward_render");
+      } else {
+        binning = empty_bytes(g_abi.binning_bytes_render_only(cap, W, H), like);
+        check(g_abi.forward_render_only(dev.stream, P, W, H, cap, fp(bg), geom.data_ptr(), tiles.data_ptr(), binning.data_ptr(), fp(color), 0),
+              "raster_forward_render_only");
+      }
+    };
+    preprocess();
+    R = capacity;
+    if (R >= 0) {
+      stage2(R);   // the caller's bound: no host synchronisation at all (BinningPolicy "bounded"; it verifies the count later)
+      return;
+    }
+    // The reference operator's own blocking read-back of the instance count (its forward sizes the sort buffers from it).
+    // The blocking semantics are kept — the call returns knowing the exact count, and no instance was dropped — but the GPU
+    // does not sit idle through the round trip: when a count of an earlier frame like this one is known (`count_hint`),
+    // stage 2 is enqueued at once in buffers sized from it, and the host then merely waits for the count word, which the
+    // tile-scan kernel stores straight into pinned host memory.  A frame that outgrew the guess is projected and rendered a
+    // second time with exact buffers (identical result; rare: the guess is 1.5 x + 16384).
+    const int64_t guess = count_hint > 0 ? count_hint + count_hint / 2 + 16384 : -1;
+    if (guess > 0) stage2(guess);
+    {
+      HostClock wait_clock(&g_host_us[5]);
+      wait_for_count(count, dev, like);
+    }
+    R = *reinterpret_cast<volatile int32_t*>(count);
+    if (guess > 0 && R <= guess) {
+      R = guess;
+    } else {
+      if (guess > 0) {   // the overflowing stage 2 consumed the tile cursors: start the frame again
+        preprocess();
+        wait_for_count(count, dev, like);
+      }
+      stage2(R);
+    }
+  }
+};
+
+// The backward's side of `FrameForward::scratch`: the accumulator buffer the forward allocated and had cleared — once: a second
+// backward of the same frame (retain_graph) finds it used and lets the library clear it, as does a frame whose forward saved
+// none.  -> the buffer and the `scratch_is_clear` argument of the library's backward; the frame's buffers are checked on the way.
+std::pair<Tensor, int> backward_scratch(AutogradContext* ctx, Tensor scratch, const Tensor& like, const Tensor& binning, int64_t R, int P,
+                                        int W, int H) {
+  const int is_clear = (scratch.defined() && ctx->saved_data["scratch_is_clear"].toBool()) ? 1 : 0;
+  ctx->saved_data["scratch_is_clear"] = false;
+  if (!scratch.defined()) scratch = empty_bytes(g_abi.grad_scratch_bytes(P), like);
+  check_frame_buffers(binning, scratch, R, P, W, H);
+  return {scratch, is_clear};
+}
+
+// ------------------------------------------------------------------------------------------------
 // render()'s differentiable body: raw GaussianModel tensors + the 7-vector camera pose in, image out
 // (reference gaussian_renderer/__init__.py:81-135; the Python twin is instantsplat_amd/fused.py::_RenderPosed)
 // ------------------------------------------------------------------------------------------------
@@ -348,84 +421,33 @@ struct RenderPosedFn : public torch::autograd::Function<RenderPosedFn> {
                  pose = f32c(pose_, "camera_pose", xyz), bg = f32c(bg_, "bg", xyz), view = f32c(view_, "viewmatrix", xyz),
                  proj = f32c(proj_, "projmatrix", xyz), origin = f32c(origin_, "campos", xyz);
     TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "means3D must have dimensions (num_points, 3)");
-    TORCH_CHECK(count_slot.scalar_type() == at::kInt && count_slot.numel() == 1, "count_slot must be one int32");
     const int P = (int)xyz.size(0);
     const DeviceScope dev(xyz);
-    Tensor radii = at::empty({P}, xyz.options().dtype(at::kInt));
+    FrameForward f(xyz, P, count_slot);
     Tensor visible = at::empty({P}, xyz.options().dtype(at::kBool));   // radii > 0, written by the projection kernel
-    Tensor color = at::empty({3, H, W}, xyz.options());
-    Tensor geom = empty_bytes(g_abi.geom_bytes(P), xyz), tiles = empty_bytes(g_abi.tiles_bytes((int)W, (int)H), xyz);
-    // a backward will follow: its accumulator buffer is allocated now and cleared by the projection kernel on its way
-    Tensor scratch;
-    if (t_backward_follows && g_forward_owns_scratch) scratch = empty_bytes(g_abi.grad_scratch_bytes(P), xyz);
-    int32_t* count = count_slot.data_ptr<int32_t>();  // pinned host memory the tile-scan kernel stores into (a CPU word under emulation)
-    auto preprocess = [&]() {
-      *reinterpret_cast<volatile int32_t*>(count) = -1;   // "not written yet" for wait_for_count
+    f.run(dev, xyz, P, (int)W, (int)H, bg, capacity, count_hint, [&](const FrameForward& frame) {
       check(g_abi.posed_forward_preprocess(dev.stream, P, (int)D, (int)W, (int)H, fp(xyz), fp(f_dc), fp(f_rest), fp(opl), fp(scaling),
                                            (float)scale_modifier, fp(rot), fp(pose), fp(view), fp(proj), fp(origin), (float)tanfovx,
-                                           (float)tanfovy, radii.data_ptr<int32_t>(), geom.data_ptr(), tiles.data_ptr(), count,
+                                           (float)tanfovy, frame.radii.data_ptr<int32_t>(), frame.geom.data_ptr(), frame.tiles.data_ptr(), frame.count,
                                            P > 0 ? reinterpret_cast<uint8_t*>(visible.data_ptr<bool>()) : nullptr,
-                                           scratch.defined() ? scratch.data_ptr() : nullptr, 0),
+                                           frame.scratch.defined() ? frame.scratch.data_ptr() : nullptr, 0),
             "posed_forward_preprocess");
-    };
-    Tensor binning;
-    // no backward will follow (nothing requires a gradient, or grad mode is off where the operator was called): the render-only
-    // stage 2 — a binning buffer of keys + lists only, no boundary records / hit masks / unit table left for a backward
-    const bool train = t_backward_follows || !g_render_only_when_no_grad;
-    auto stage2 = [&](int64_t cap) {
-      if (train) {
-        binning = empty_bytes(g_abi.binning_bytes(cap, (int)W, (int)H), xyz);
-        check(g_abi.forward_render(dev.stream, P, (int)W, (int)H, cap, fp(bg), geom.data_ptr(), tiles.data_ptr(), binning.data_ptr(),
-                                   fp(color), 0),
-              "raster_forward_render");
-      } else {
-        binning = empty_bytes(g_abi.binning_bytes_render_only(cap, (int)W, (int)H), xyz);
-        check(g_abi.forward_render_only(dev.stream, P, (int)W, (int)H, cap, fp(bg), geom.data_ptr(), tiles.data_ptr(), binning.data_ptr(),
-                                        fp(color), 0),
-              "raster_forward_render_only");
-      }
-    };
-    preprocess();
-    int64_t R = capacity;
-    if (R >= 0) {
-      stage2(R);   // the caller's bound: no host synchronisation at all (BinningPolicy "bounded"; it verifies the count later)
-    } else {
-      // The reference operator's own blocking read-back of the instance count (its forward sizes the sort buffers from it).
-      // The blocking semantics are kept — the call returns knowing the exact count, and no instance was dropped — but the GPU
-      // does not sit idle through the round trip: when a count of an earlier frame like this one is known (`count_hint`),
-      // stage 2 is enqueued at once in buffers sized from it, and the host then merely waits for the count word, which the
-      // tile-scan kernel stores straight into pinned host memory.  A frame that outgrew the guess is projected and rendered a
-      // second time with exact buffers (identical result; rare: the guess is 1.5 x + 16384).
-      const int64_t guess = count_hint > 0 ? count_hint + count_hint / 2 + 16384 : -1;
-      if (guess > 0) stage2(guess);
-      {
-        HostClock wait_clock(&g_host_us[5]);
-        wait_for_count(count, dev, xyz);
-      }
-      R = *reinterpret_cast<volatile int32_t*>(count);
-      if (guess > 0 && R <= guess) {
-        R = guess;                      // the capacity the frame's buffers were laid out for: the backward needs this number
-      } else {
-        if (guess > 0) preprocess();    // the overflowing stage 2 consumed the tile cursors: start the frame again
-        if (guess > 0) wait_for_count(count, dev, xyz);
-        stage2(R);
-      }
-    }
-    ctx->saved_data["dims"] = std::vector<int64_t>{P, D, W, H, R};
+    });
+    ctx->saved_data["dims"] = std::vector<int64_t>{P, D, W, H, f.R};
     ctx->saved_data["scalars"] = std::vector<double>{tanfovx, tanfovy, scale_modifier};
-    ctx->saved_data["scratch_is_clear"] = scratch.defined();
+    ctx->saved_data["scratch_is_clear"] = f.scratch.defined();
     {
       // is the pose the row get_RT just handed out on this thread?  Then the backward writes the table's gradient (PoseRowFn)
       auto seen = t_pose_row.row.lock();
       const bool is_row = seen && seen.get() == pose_.unsafeGetTensorImpl() && t_pose_row.rows > 0;
       ctx->saved_data["pose_table"] = std::vector<int64_t>{is_row ? t_pose_row.rows : 0, is_row ? t_pose_row.index : 0};
     }
-    ctx->save_for_backward({xyz, rot, scaling, opl, f_dc, f_rest, pose, radii, geom, tiles, binning, bg, view, proj, origin, color,
-                            scratch.defined() ? scratch : Tensor()});
-    ctx->mark_non_differentiable({radii, visible});
+    ctx->save_for_backward({xyz, rot, scaling, opl, f_dc, f_rest, pose, f.radii, f.geom, f.tiles, f.binning, bg, view, proj, origin, f.color,
+                            f.scratch});
+    ctx->mark_non_differentiable({f.radii, visible});
     // (no zero tensors for the gradients of `radii` / `visible`: autograd otherwise fills one of each per backward — two launches)
     ctx->set_materialize_grads(false);
-    return {color, radii, visible};
+    return {f.color, f.radii, visible};
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
@@ -454,14 +476,8 @@ struct RenderPosedFn : public torch::autograd::Function<RenderPosedFn> {
       d_pose = at::empty({0}, xyz.options());
       d_pose.set_(d_pose_store.storage(), 7 * pose_index, {7}, {1});
     }
-    // the accumulator buffer the forward allocated and had cleared — once: a second backward of the same frame (retain_graph)
-    // finds it used and lets the library clear it
-    Tensor scratch = saved.size() > 16 ? saved[16] : Tensor();
-    int scratch_is_clear = (scratch.defined() && ctx->saved_data["scratch_is_clear"].toBool()) ? 1 : 0;
-    ctx->saved_data["scratch_is_clear"] = false;
-    if (!scratch.defined()) scratch = empty_bytes(g_abi.grad_scratch_bytes(P), xyz);
+    const auto [scratch, scratch_is_clear] = backward_scratch(ctx, saved[16], xyz, binning, R, P, W, H);
     Tensor pose_scratch = at::empty({16 * (((int64_t)P + 255) / 256) + 32}, xyz.options());
-    check_frame_buffers(binning, scratch, R, P, W, H);
     check(g_abi.posed_backward(dev.stream, P, D, W, H, fp(bg), fp(xyz), fp(f_dc), fp(f_rest), fp(opl), fp(scaling), (float)sc[2], fp(rot),
                                fp(pose), fp(view), fp(proj), fp(origin), (float)sc[0], (float)sc[1], geom.data_ptr(), tiles.data_ptr(),
                                binning.data_ptr(), R, radii.data_ptr<int32_t>(), fp(color), fp(g), scratch.data_ptr(), fp(pose_scratch),
@@ -526,66 +542,26 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     const Tensor bg = f32c(bg_, "bg", means3D), view = f32c(view_, "viewmatrix", means3D), proj = f32c(proj_, "projmatrix", means3D),
                  campos = f32c(campos_, "campos", means3D);
     TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
-    TORCH_CHECK(count_slot.scalar_type() == at::kInt && count_slot.numel() == 1, "count_slot must be one int32");
     const int P = (int)means3D.size(0);
     const int M = sh.defined() ? (int)(sh.size(1) + (sh_rest.defined() ? sh_rest.size(1) : 0)) : 0;
     const DeviceScope dev(means3D);
-    Tensor radii = at::empty({P}, means3D.options().dtype(at::kInt));
-    Tensor color = at::empty({3, H, W}, means3D.options());
-    Tensor geom = empty_bytes(g_abi.geom_bytes(P), means3D), tiles = empty_bytes(g_abi.tiles_bytes((int)W, (int)H), means3D);
-    Tensor scratch;   // see RenderPosedFn::forward
-    if (t_backward_follows && g_forward_owns_scratch) scratch = empty_bytes(g_abi.grad_scratch_bytes(P), means3D);
-    int32_t* count = count_slot.data_ptr<int32_t>();
-    auto preprocess = [&]() {
-      *reinterpret_cast<volatile int32_t*>(count) = -1;
+    FrameForward f(means3D, P, count_slot);
+    f.run(dev, means3D, P, (int)W, (int)H, bg, capacity, count_hint, [&](const FrameForward& frame) {
       check(g_abi.forward_preprocess(dev.stream, P, (int)D, M, (int)W, (int)H, fp(means3D), fp(sh), fp(sh_rest), fp(colors), fp(opac), fp(scales),
                                      (float)scale_modifier, fp(rot), fp(cov), fp(view), fp(proj), fp(campos), (float)tanfovx, (float)tanfovy,
-                                     prefiltered ? 1 : 0, radii.data_ptr<int32_t>(), geom.data_ptr(), tiles.data_ptr(), count, nullptr,
-                                     scratch.defined() ? scratch.data_ptr() : nullptr, 0),
+                                     prefiltered ? 1 : 0, frame.radii.data_ptr<int32_t>(), frame.geom.data_ptr(), frame.tiles.data_ptr(), frame.count, nullptr,
+                                     frame.scratch.defined() ? frame.scratch.data_ptr() : nullptr, 0),
             "raster_forward_preprocess");
-    };
-    Tensor binning;
-    const bool train = t_backward_follows || !g_render_only_when_no_grad;   // see RenderPosedFn::forward
-    auto stage2 = [&](int64_t cap) {
-      if (train) {
-        binning = empty_bytes(g_abi.binning_bytes(cap, (int)W, (int)H), means3D);
-        check(g_abi.forward_render(dev.stream, P, (int)W, (int)H, cap, fp(bg), geom.data_ptr(), tiles.data_ptr(), binning.data_ptr(), fp(color), 0),
-              "raster_forward_render");
-      } else {
-        binning = empty_bytes(g_abi.binning_bytes_render_only(cap, (int)W, (int)H), means3D);
-        check(g_abi.forward_render_only(dev.stream, P, (int)W, (int)H, cap, fp(bg), geom.data_ptr(), tiles.data_ptr(), binning.data_ptr(),
-                                        fp(color), 0),
-              "raster_forward_render_only");
-      }
-    };
-    preprocess();
-    int64_t R = capacity;
-    if (R >= 0) {
-      stage2(R);
-    } else {   // blocking count read-back with a speculative stage 2: see RenderPosedFn::forward
-      const int64_t guess = count_hint > 0 ? count_hint + count_hint / 2 + 16384 : -1;
-      if (guess > 0) stage2(guess);
-      {
-        HostClock wait_clock(&g_host_us[5]);
-        wait_for_count(count, dev, means3D);
-      }
-      R = *reinterpret_cast<volatile int32_t*>(count);
-      if (guess > 0 && R <= guess) {
-        R = guess;
-      } else {
-        if (guess > 0) { preprocess(); wait_for_count(count, dev, means3D); }
-        stage2(R);
-      }
-    }
-    ctx->saved_data["dims"] = std::vector<int64_t>{P, D, M, W, H, R};
+    });
+    ctx->saved_data["dims"] = std::vector<int64_t>{P, D, M, W, H, f.R};
     ctx->saved_data["scalars"] = std::vector<double>{tanfovx, tanfovy, scale_modifier};
     ctx->saved_data["opacity_shape"] = opac_.sizes().vec();
-    ctx->saved_data["scratch_is_clear"] = scratch.defined();
-    ctx->save_for_backward({means3D, sh, colors, opac, scales, rot, cov, sh_rest, radii, geom, tiles, binning, bg, view, proj, campos, color,
-                            scratch.defined() ? scratch : Tensor()});
-    ctx->mark_non_differentiable({radii});
+    ctx->saved_data["scratch_is_clear"] = f.scratch.defined();
+    ctx->save_for_backward({means3D, sh, colors, opac, scales, rot, cov, sh_rest, f.radii, f.geom, f.tiles, f.binning, bg, view, proj, campos,
+                            f.color, f.scratch});
+    ctx->mark_non_differentiable({f.radii});
     ctx->set_materialize_grads(false);
-    return {color, radii};
+    return {f.color, f.radii};
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grad_out) {
@@ -606,11 +582,7 @@ struct RasterizeFn : public torch::autograd::Function<RasterizeFn> {
     if (sh.defined()) d_sh = at::empty({P, sh_rest.defined() ? 1 : M, 3}, o);
     if (sh_rest.defined()) d_shr = at::empty({P, M - 1, 3}, o);
     if (cov.defined()) d_cov = at::empty({P, 6}, o); else { d_scales = at::empty({P, 3}, o); d_rot = at::empty({P, 4}, o); }
-    Tensor scratch = saved.size() > 17 ? saved[17] : Tensor();
-    const int scratch_is_clear = (scratch.defined() && ctx->saved_data["scratch_is_clear"].toBool()) ? 1 : 0;
-    ctx->saved_data["scratch_is_clear"] = false;
-    if (!scratch.defined()) scratch = empty_bytes(g_abi.grad_scratch_bytes(P), means3D);
-    check_frame_buffers(binning, scratch, R, P, W, H);
+    const auto [scratch, scratch_is_clear] = backward_scratch(ctx, saved[17], means3D, binning, R, P, W, H);
     check(g_abi.raster_backward(dev.stream, P, D, M, W, H, fp(bg), fp(means3D), fp(sh), fp(sh_rest), fp(colors), fp(opac), fp(scales), (float)sc[2],
                                 fp(rot), fp(cov), fp(view), fp(proj), fp(campos), (float)sc[0], (float)sc[1], geom.data_ptr(), tiles.data_ptr(),
                                 binning.data_ptr(), R, radii.data_ptr<int32_t>(), fp(color), fp(g), scratch.data_ptr(), fp(d_means3D), fp(d_means2D),
@@ -1024,13 +996,10 @@ struct AdamPlan {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "compiled PyTorch binding of libmi355gs.so's drop-in operators (no compute of its own)";
+  m.def("abi_symbols", &abi_symbols, "the C symbols bind() must be given, in the order of the list they are generated from");
   m.def("bind", &bind_abi, "hand over the C-ABI entry points (name -> address) of the loaded libmi355gs build; allow_cpu_tensors: test tier only");
-  m.def("l1_loss", &l1_loss, "utils/loss_utils.py::l1_loss as one node (mi355gs_l1_loss_forward / _backward)");
+  m.def("l1_loss", &l1_loss, "utils/loss_utils.py::l1_loss as one node (the library's l1_loss forward / backward pair)");
   m.def("render_posed", &render_posed);
-  m.def("forward_owns_scratch", [](bool on) { const bool was = g_forward_owns_scratch; g_forward_owns_scratch = on; return was; },
-        "A/B switch: true (default) = a forward that a backward will follow allocates the backward's accumulators and has the projection kernel clear them");
-  m.def("render_only", [](bool on) { const bool was = g_render_only_when_no_grad; g_render_only_when_no_grad = on; return was; },
-        "A/B switch: true (default) = a forward no backward can follow takes the render-only stage 2 (mi355gs_raster_forward_render_only)");
   m.def("wait_for_words", &wait_for_words, "spin (GIL released) until no element of an int32 pinned host tensor holds the sentinel; stream wait after timeout_us");
   m.def("pose_row", &pose_row, "GaussianModel.get_RT: row `index` of the [views, 7] pose table as a node the render node's backward cooperates with");
   m.def("rasterize", &rasterize);

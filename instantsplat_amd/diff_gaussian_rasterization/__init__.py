@@ -7,6 +7,7 @@ Same public names, argument meaning and error behaviour as that operator package
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import NamedTuple
 
 import torch
@@ -185,7 +186,6 @@ class binning_hint:
         BinningPolicy.current_key, BinningPolicy.current_tag = self.prev
 
 
-RENDER_ONLY_WHEN_NO_GRAD = True   # A/B switch of this (ctypes) binding; the compiled one has ext.render_only(bool)
 _BACKWARD_FOLLOWS = [True]        # set by the callers of the Python nodes around apply(): inside forward() grad mode is off
 
 
@@ -222,7 +222,7 @@ def size_and_render(L, stream, dev, P, W, H, num_rendered, bg, geom, tiles, colo
         R = int(num_rendered[0])
         if key is not None:
             BinningPolicy.known[key] = R
-    if _BACKWARD_FOLLOWS[0] or not RENDER_ONLY_WHEN_NO_GRAD:
+    if _BACKWARD_FOLLOWS[0]:
         binning = _empty_bytes(L.mi355gs_raster_binning_bytes(R, W, H), dev)
         _lib.check(L.mi355gs_raster_forward_render(stream, P, W, H, R, _lib.ptr(bg), _lib.ptr(geom), _lib.ptr(tiles),
                                                    _lib.ptr(binning), _lib.ptr(color), debug), "raster_forward_render")
@@ -347,6 +347,33 @@ def read_count(slot) -> int:
     return int(slot[0])
 
 
+_LAST_COUNT = {}   # (node, P, W, H, hint key) -> instance count of the last frame like this one (sizes the speculative stage 2)
+
+
+def compiled_frame(node, P, W, H, dev, call):
+    """A frame through a compiled node (csrc_torch/binding.cpp) with the BinningPolicy bookkeeping of `size_and_render` around
+    it: `call(capacity, count_hint, slot)` invokes the node (a functools.partial over its other arguments) and its outputs are
+    returned.  `node` names it ("posed" / "raster"): a frame takes its hint only from an earlier frame of the same node."""
+    slot = count_slot(dev)
+    cap = BinningPolicy.deferred_capacity()
+    if cap is not None:
+        out = call(cap, 0, slot)
+        BinningPolicy.defer(slot, cap, dev)
+        return out
+    # exact mode: the reference operator's blocking count read-back; the count of the previous frame like this one lets the
+    # node enqueue stage 2 before the count of THIS frame has arrived (see FrameForward::run)
+    key = BinningPolicy.current_key
+    ck = (node, P, W, H, key)
+    out = call(-1, _LAST_COUNT.get(ck, 0), slot)
+    r = read_count(slot)
+    if len(_LAST_COUNT) > 256:
+        _LAST_COUNT.clear()
+    _LAST_COUNT[ck] = r
+    if key is not None:
+        BinningPolicy.known[key] = r
+    return out
+
+
 def _cpu_deep_copy_tuple(input_tuple):
     return tuple(item.cpu().clone() if isinstance(item, torch.Tensor) else item for item in input_tuple)
 
@@ -456,9 +483,6 @@ class _RasterizeGaussians(torch.autograd.Function):
                 dL_dscales, dL_drot, dL_dcov, None, dL_dshr)
 
 
-_LAST_COUNT = {}   # (P, W, H, hint key) -> instance count of the last frame like this one (sizes the speculative stage 2)
-
-
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
                         sh_rest=None):
     s = raster_settings
@@ -467,27 +491,13 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         with backward_follows(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, sh_rest):
             return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                              raster_settings, sh_rest)
-    # the compiled node (csrc_torch/binding.cpp::RasterizeFn): the same three C-ABI calls, with size_and_render's bookkeeping here
+    # the compiled node (csrc_torch/binding.cpp::RasterizeFn): the same three C-ABI calls
     opt = lambda t: None if (t is None or t.numel() == 0) else t
-    dev = means3D.device
     H, W = int(s.image_height), int(s.image_width)
-    slot = count_slot(dev)
-    cap = BinningPolicy.deferred_capacity()
-    key = BinningPolicy.current_key
-    ck = (means3D.shape[0], W, H, key)
-    color, radii = ext.rasterize(means3D, means2D, opt(sh), opt(colors_precomp), opacities, opt(scales), opt(rotations), opt(cov3Ds_precomp),
-                                 opt(sh_rest), s.bg, s.viewmatrix, s.projmatrix, s.campos, H, W, float(s.tanfovx), float(s.tanfovy),
-                                 float(s.scale_modifier), int(s.sh_degree), bool(s.prefiltered), -1 if cap is None else cap,
-                                 0 if cap is not None else _LAST_COUNT.get(ck, 0), slot)
-    if cap is not None:
-        BinningPolicy.defer(slot, cap, dev)
-    else:
-        r = int(slot[0])
-        if len(_LAST_COUNT) > 256:
-            _LAST_COUNT.clear()
-        _LAST_COUNT[ck] = r
-        if key is not None:
-            BinningPolicy.known[key] = r
+    color, radii = compiled_frame("raster", means3D.shape[0], W, H, means3D.device, partial(
+        ext.rasterize, means3D, means2D, opt(sh), opt(colors_precomp), opacities, opt(scales), opt(rotations), opt(cov3Ds_precomp),
+        opt(sh_rest), s.bg, s.viewmatrix, s.projmatrix, s.campos, H, W, float(s.tanfovx), float(s.tanfovy), float(s.scale_modifier),
+        int(s.sh_degree), bool(s.prefiltered)))
     return color, radii
 
 

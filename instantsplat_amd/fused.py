@@ -8,6 +8,8 @@ including the reduction over every Gaussian to the seven pose gradients.
 """
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 
 from . import _lib
@@ -140,35 +142,14 @@ class _RenderPosed(torch.autograd.Function):
         return d_xyz, d_rot, d_scaling, d_opl, d_fdc, d_frest, d_pose, d_m2d, None
 
 
-_LAST_COUNT = {}   # (P, W, H, hint key) -> instance count of the last frame like this one (sizes the speculative stage 2)
-
-
 def render_posed_compiled(ext, pc, pose, means2D, bg, view, proj, origin, H, W, tanfovx, tanfovy, scale_modifier, degree):
     """The compiled node (csrc_torch/binding.cpp) with the BinningPolicy bookkeeping of `size_and_render` around it.
     -> [image, radii, visible]: `visible` = radii > 0 as a bool tensor the projection kernel wrote (no compare kernel)."""
-    policy = dgr.BinningPolicy
     xyz = pc._xyz
-    dev = xyz.device
-    slot = dgr.count_slot(dev)
-    cap = policy.deferred_capacity()
-    key = policy.current_key
-    if cap is not None:
-        out = ext.render_posed(xyz, pc._rotation, pc._scaling, pc._opacity, pc._features_dc, pc._features_rest, pose, means2D,
-                               bg, view, proj, origin, H, W, tanfovx, tanfovy, scale_modifier, degree, cap, 0, slot)
-        policy.defer(slot, cap, dev)
-        return out
-    # exact mode: the reference operator's blocking count read-back; the count of the previous frame like this one lets the
-    # node enqueue stage 2 before the count of THIS frame has arrived (see RenderPosedFn::forward)
-    ck = (xyz.shape[0], W, H, key)
-    out = ext.render_posed(xyz, pc._rotation, pc._scaling, pc._opacity, pc._features_dc, pc._features_rest, pose, means2D,
-                           bg, view, proj, origin, H, W, tanfovx, tanfovy, scale_modifier, degree, -1, _LAST_COUNT.get(ck, 0), slot)
-    r = dgr.read_count(slot)
-    if len(_LAST_COUNT) > 256:
-        _LAST_COUNT.clear()
-    _LAST_COUNT[ck] = r
-    if key is not None:
-        policy.known[key] = r
-    return out
+    # (functools.partial: the shared function appends (capacity, count_hint, slot); no Python frame of its own on the training loop's path)
+    return dgr.compiled_frame("posed", xyz.shape[0], W, H, xyz.device, partial(
+        ext.render_posed, xyz, pc._rotation, pc._scaling, pc._opacity, pc._features_dc, pc._features_rest, pose, means2D, bg, view, proj,
+        origin, H, W, tanfovx, tanfovy, scale_modifier, degree))
 
 
 def render_posed(pc, pose, means2D, settings):

@@ -484,7 +484,7 @@ def check_speculative_stage2_overflow_is_rerendered(dev):
                 big = run(0.25, 2)          # > 20 x as many: far beyond 1.5 x + 16384
                 res[binding] = (small, big)
         from instantsplat_amd import diff_gaussian_rasterization as dgr
-        counts = [v for k, v in dgr._LAST_COUNT.items() if k[:3] == (P, W, H)]
+        counts = [v for k, v in dgr._LAST_COUNT.items() if k[1:4] == (P, W, H)]
         assert counts and max(counts) > 1.5 * 3000 + 16384 + 3000, counts   # the second frame did outgrow any guess from the first
         cuda = dev.type == "cuda"
         for i in (0, 1):

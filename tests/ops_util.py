@@ -1485,7 +1485,7 @@ def check_render_only_forward(dev, Wm=20, W=80, H=48):
     """A render no backward can follow (torch.no_grad(), or nothing requiring a gradient) takes the render-only stage 2
     (mi355gs_raster_forward_render_only: keys + lists only in `binning`, no boundary records / hit masks / unit table / quadrant
     maxima stored).  Image, radii and the per-pixel state (final_T, n_contrib -> frame statistics) must be bit-identical to the
-    training instantiation's — through render() on both bindings, through the operator, and with the switch off."""
+    training instantiation's — through render() on both bindings and through the operator."""
     import instantsplat_amd.diff_gaussian_rasterization as dgr
     from instantsplat_amd import _lib
     from instantsplat_amd.gaussian_renderer import render
@@ -1529,18 +1529,13 @@ def check_render_only_forward(dev, Wm=20, W=80, H=48):
     a = tiles_t[off_final_T: off_final_T + 8 * npix_words]
     b = tiles_r[off_final_T: off_final_T + 8 * npix_words]
     assert torch.equal(a, b)
-    # render() on the compiled binding, the switch on and off, under no_grad and with requires_grad inputs
+    # render() on the compiled binding, under no_grad and with requires_grad inputs
     ext = _lib.compiled()
     if ext is not None:
         with torch.no_grad():
             i1 = render(cam, g, st.pipe, st.background, camera_pose=pose)["render"].cpu()
-            was = ext.render_only(False)
-            try:
-                i2 = render(cam, g, st.pipe, st.background, camera_pose=pose)["render"].cpu()
-            finally:
-                ext.render_only(was)
         i3 = render(cam, g, st.pipe, st.background, camera_pose=pose)["render"].detach().cpu()
-        assert torch.equal(i1, img_t) and torch.equal(i2, img_t) and torch.equal(i3, img_t)
+        assert torch.equal(i1, img_t) and torch.equal(i3, img_t)
     # a training render right after a render-only one of the same view still gives the gradients of the training path
     for t in (g._xyz, g._opacity, g.P):
         t.grad = None
