@@ -447,6 +447,8 @@ const float* mi355gs_trainer_grad(void* trainer, int k);
  *   Overflow: an iteration whose instance count exceeds the capacity sets the sticky flag; it and every later iteration of
  *   that state leave pose, moments, best and candidate unchanged.  The count slot holds the largest count seen.
  *   count: the exact instance count at `pose` (device float[7]) into *count_out (device int32), for sizing the capacity.
+ *   Streams: a tracker (and a trainer) handle writes its identity view / zero camera position once, on the stream of its first
+ *   call; use a handle on ONE stream, or order its first call before calls on another.
  * ---------------------------------------------------------------------------------------------- */
 #define MI355GS_TRACKER_STATE_FLOATS 40
 #define MI355GS_TRACKER_POSE 0        /* [7] current pose */
@@ -466,6 +468,34 @@ int mi355gs_tracker_run(void* tracker, void* stream, int sh_degree, const float*
                         float tanfovy, const float* bg, const float* sched, int num_iter, int first_iter, int n_iters, float* state,
                         float* pose_trace, float* loss_trace, float* grad_trace);
 void mi355gs_tracker_destroy(void* tracker);
+
+/* ----------------------------------------------------------------------------------------------
+ * Camera paths (reference render.py:78-97, `render_set`, and its --infer_video stage :233-248): a list of poses rendered to
+ * 8-bit frames with the Gaussians frozen and no gradient.
+ *
+ *   rgb8_from_planar: img [3,H,W] float -> out [H,W,3] uint8 with the arithmetic of torchvision.utils.save_image
+ *   (x.mul(255).add_(0.5).clamp_(0, 255).to(uint8): an fp32 multiply and an fp32 add, each rounded once, clamp, truncation);
+ *   a NaN gives 0.  out: device memory or pinned host memory mapped into the device's address space.  One launch.
+ *
+ *   path handle, shaped like the tracker's: raw Gaussian parameters (read only; f_dc [P,3], f_rest [P,M-1,3] or null when
+ *   M == 1), the fixed image size and instance capacity; workspace: mi355gs_path_workspace_bytes() bytes, owned by the caller
+ *   (projection records, tile tables, the render-only binning buffer, radii, one [3,H,W] float image).  Nothing allocates.
+ *   render: enqueues, for every pose i of first .. first+n-1 of poses (device float[N][7], (qw,qx,qy,qz,tx,ty,tz)), the posed
+ *   projection, the binning and the render-only compositing at the handle's capacity, and one launch that converts the image
+ *   into frames + i*H*W*3 (uint8 [N][H][W][3]; device memory or mapped pinned host memory) and copies the frame's true instance
+ *   count to counts[i] (device int32[N]): 7 launches per frame (and one 2 us launch per call that writes the handle's identity
+ *   view / zero camera position on the call's stream, so a handle may be used on any stream, one call at a time), no memset, no
+ *   host synchronisation, no event, no copy.
+ *   Slots outside the range are not touched.  Frame i is valid exactly when counts[i] <= capacity; an overflowed frame holds
+ *   the truncated render of mi355gs_raster_forward_render_only.  Overflow is per frame, not sticky: frames are independent.
+ * ---------------------------------------------------------------------------------------------- */
+int mi355gs_rgb8_from_planar(void* stream, int H, int W, const float* img, uint8_t* out);
+size_t mi355gs_path_workspace_bytes(int P, int W, int H, int64_t capacity);
+void* mi355gs_path_create(int P, int M, int W, int H, int64_t capacity, const float* xyz, const float* f_dc, const float* f_rest,
+                          const float* opacity, const float* scaling, const float* rotation, void* workspace);
+int mi355gs_path_render(void* path, void* stream, int sh_degree, const float* projmatrix, float tanfovx, float tanfovy,
+                        const float* bg, const float* poses, int first, int n, uint8_t* frames, int32_t* counts);
+void mi355gs_path_destroy(void* path);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,11 @@ _SIGNATURES = {
     "mi355gs_tracker_count": (c_int, [_P, _P, c_int, _P, c_float, c_float, _P, _P]),
     "mi355gs_tracker_run": (c_int, [_P, _P, c_int, _P, _P, c_float, c_float, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "mi355gs_tracker_destroy": (None, [_P]),
+    "mi355gs_rgb8_from_planar": (c_int, [_P, c_int, c_int, _P, _P]),
+    "mi355gs_path_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int64]),
+    "mi355gs_path_create": (c_void_p, [c_int, c_int, c_int, c_int, c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "mi355gs_path_render": (c_int, [_P, _P, c_int, _P, c_float, c_float, _P, _P, c_int, c_int, _P, _P]),
+    "mi355gs_path_destroy": (None, [_P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -115,6 +115,18 @@ static CamParams make_cam(const float* view, const float* proj, const float* cam
 
 static inline uint32_t clamp_capacity(int64_t c) { return c <= 0 ? 0u : (c > 0x7fffffffLL ? 0x7fffffffu : (uint32_t)c); }
 
+// the handles' device constants (common.h)
+namespace {
+__global__ void k_view_consts(float* consts) {
+  const int i = threadIdx.x;
+  if (i < 16) consts[i] = (i % 5 == 0) ? 1.f : 0.f;  // identity view matrix
+  else if (i < 19) consts[i] = 0.f;                   // camera position
+}
+}  // namespace
+void gs_launch_view_consts(hipStream_t stream, float* consts) {
+  hipLaunchKernelGGL(k_view_consts, dim3(1), dim3(64), 0, stream, consts);
+}
+
 extern "C" {
 
 int mi355gs_abi_version(void) { return MI355GS_ABI_VERSION; }

@@ -34,6 +34,21 @@ struct alignas(16) GsGrad {
 
 static inline size_t gs_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Carves a handle's buffers out of one caller-provided workspace (trainer, tracker, path): take<T>(n) returns the next
+// 256-byte-aligned block of n elements; with a null base it only counts, which is how the *_workspace_bytes queries size it.
+struct GsCarver {
+  char* base;
+  size_t off = 0;
+  template <class T> T* take(size_t n) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += gs_align(n * sizeof(T));
+    return p;
+  }
+};
+// The device constants InstantSplat's render() hands the operator (reference gaussian_renderer/__init__.py:55-59), written by
+// one tiny launch (api.hip): consts[0..15] = the identity view matrix, consts[16..18] = the camera position 0.
+void gs_launch_view_consts(hipStream_t stream, float* consts);
+
 // Binning (binning.hip): a workgroup counts / scatters GS_BIN_CHUNK consecutive Gaussians; the count kernel leaves each
 // workgroup's touched tiles as up to GS_BIN_ENTRIES packed (tile | count << 16) words for the scatter kernel of the same frame.
 constexpr int GS_BIN_CHUNK = 512;

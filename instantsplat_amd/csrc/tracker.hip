@@ -33,18 +33,8 @@ struct Tracker {
   int det, min_units;   // the knobs as they stood at create: the buffers were laid out for them
 };
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  template <class T> T* take(size_t n) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += gs_align(n * sizeof(T));
-    return p;
-  }
-};
-
 size_t carve(Tracker& t, void* workspace) {
-  Carver c{(char*)workspace};
+  GsCarver c{(char*)workspace};
   const size_t P = (size_t)(t.P > 0 ? t.P : 1), npix = (size_t)t.W * t.H;
   t.geom = c.take<char>(mi355gs_raster_geom_bytes(t.P));
   t.tiles = c.take<char>(mi355gs_raster_tiles_bytes(t.W, t.H));
@@ -57,12 +47,6 @@ size_t carve(Tracker& t, void* workspace) {
   t.radii = c.take<int32_t>(P);
   t.num_rendered = c.take<int32_t>(1);
   return c.off;
-}
-
-__global__ void k_tracker_consts(float* consts) {
-  const int i = threadIdx.x;
-  if (i < 16) consts[i] = (i % 5 == 0) ? 1.f : 0.f;  // identity view matrix
-  else if (i < 19) consts[i] = 0.f;                   // camera position
 }
 
 // Masked L1 (reference utils/loss_utils.py:17-23 with mask = render > 0): per workgroup the partial sums of |r - gt| * m and of
@@ -229,7 +213,7 @@ int ensure_consts(Tracker* t, hipStream_t stream) {
   const int debug = 0;
   if (t->consts_ready) return MI355GS_OK;
   GS_KRANGE("tracker_consts");
-  hipLaunchKernelGGL(k_tracker_consts, dim3(1), dim3(64), 0, stream, t->consts);
+  gs_launch_view_consts(stream, t->consts);
   GS_CHECK_LAUNCH("tracker_consts");
   t->consts_ready = true;
   return MI355GS_OK;

@@ -47,18 +47,8 @@ struct Trainer {
                    // out for it)
 };
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  template <class T> T* take(size_t n) {
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += gs_align(n * sizeof(T));
-    return p;
-  }
-};
-
 size_t carve(Trainer& t, void* workspace) {
-  Carver c{(char*)workspace};
+  GsCarver c{(char*)workspace};
   const size_t P = (size_t)(t.P > 0 ? t.P : 1), npix = (size_t)t.W * t.H;
   t.geom = c.take<char>(mi355gs_raster_geom_bytes(t.P));
   t.tiles = c.take<char>(mi355gs_raster_tiles_bytes(t.W, t.H));
@@ -94,12 +84,6 @@ int trainer_adam(Trainer* t, hipStream_t stream, const float* lr, const int32_t*
     g_fused.commit_poison = t->adam_live + 15;   // (words 0..13 are MultiAdamArgs::live's; cleared with them before the first step)
   }
   return mi355gs_adam_multi_step(stream, 7, numel, row, params, grads, t->m, t->v, pplr, lr, beta1, beta2, eps, step, t->adam_scratch, nullptr, nullptr, nullptr, 0u);
-}
-
-__global__ void k_trainer_consts(float* consts) {
-  const int i = threadIdx.x;
-  if (i < 16) consts[i] = (i % 5 == 0) ? 1.f : 0.f;  // identity view matrix
-  else if (i < 19) consts[i] = 0.f;                   // camera position
 }
 
 }  // namespace
@@ -210,7 +194,7 @@ int mi355gs_trainer_step(void* handle, void* stream_, int view, int sh_degree, c
   const int P = t->P, W = t->W, H = t->H;
   if (!t->consts_ready) {
     GS_KRANGE("trainer_consts");
-    hipLaunchKernelGGL(k_trainer_consts, dim3(1), dim3(64), 0, stream, t->consts);
+    gs_launch_view_consts(stream, t->consts);
     GS_CHECK_LAUNCH("trainer_consts");
     // at SH degree 0 f_rest receives no gradient: its (all-zero) gradient buffer is written once here and first
     // touched again when the degree is raised (the backward then rewrites every element each step)

@@ -1,0 +1,260 @@
+"""Rendering a list of camera poses to 8-bit frames — the reference's `render_set` (render.py:78-97) and its `--infer_video`
+stage (:233-248): the train-view renders of a trained scene, and the fly-through along the interpolated path of its poses.
+
+`render_pose_path` runs the whole list on the device (csrc/path.hip, include/mi355gs.h mi355gs_path_*): one library call
+enqueues every frame of a group of views — posed projection, binning, render-only compositing, 8-bit conversion straight into the
+[N,H,W,3] frame array — with one read-back of the per-frame instance counts at the end.  `quantize_rgb8` is the conversion
+alone (torchvision.utils.save_image's arithmetic), `render_set` writes the files, `render_interpolated` is the third stage of
+the reference's run_infer.sh after `train.training()`.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes
+import math
+import os
+from typing import List
+
+import numpy as np
+import torch
+
+from . import _lib
+from .camera_path import save_interpolate_pose
+from .diff_gaussian_rasterization import BinningPolicy
+from .gaussian_renderer import render
+from .pose_utils import get_tensor_from_camera
+from .scene_io import load_cameras
+
+
+def quantize_rgb8(image: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """[3,H,W] float32 -> [H,W,3] uint8 as torchvision.utils.save_image quantises: x.mul(255).add_(0.5).clamp_(0, 255).to(uint8),
+    a NaN giving 0.  One launch (mi355gs_rgb8_from_planar)."""
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError(f"quantize_rgb8 takes a [3,H,W] image, got {tuple(image.shape)}")
+    image = _lib.f32c(image.detach())
+    dev = _lib.require_device(image)
+    H, W = int(image.shape[1]), int(image.shape[2])
+    if out is None:
+        out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous():
+        raise ValueError(f"quantize_rgb8 writes a contiguous uint8 [{H},{W},3] tensor")
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().mi355gs_rgb8_from_planar(_lib.stream_ptr(dev), H, W, _lib.ptr(image), _lib.ptr(out)), "rgb8_from_planar")
+    return out
+
+
+class FusedPathRenderer:
+    """Handle of mi355gs_path_*: the frozen Gaussians' raw parameters, one image size and an instance capacity."""
+
+    def __init__(self, gaussians, W: int, H: int, capacity: int):
+        g = gaussians
+        self.params = [t.detach() for t in (g._xyz, g._features_dc, g._features_rest, g._opacity, g._scaling, g._rotation)]
+        dev = _lib.require_device(*self.params)
+        P = int(self.params[0].shape[0])
+        M = 1 + int(self.params[2].shape[1]) if self.params[2].dim() == 3 else 1
+        shapes = ((P, 3), (P, 1, 3), (P, M - 1, 3), (P, 1), (P, 3), (P, 4))
+        for t, shape in zip(self.params, shapes):   # the library indexes raw pointers with these shapes
+            if t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise ValueError(f"path rendering needs float32 parameters of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+        L = _lib.lib()
+        self.dev, self.P, self.M, self.W, self.H, self.capacity = dev, P, M, int(W), int(H), int(capacity)
+        nbytes = L.mi355gs_path_workspace_bytes(P, self.W, self.H, self.capacity)
+        if not nbytes:
+            raise ValueError("mi355gs_path_workspace_bytes rejected the sizes")
+        self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        self.handle = L.mi355gs_path_create(P, M, self.W, self.H, self.capacity, *[_lib.ptr(t) for t in self.params],
+                                            _lib.ptr(self.workspace))
+        if not self.handle:
+            raise RuntimeError("mi355gs_path_create failed")
+
+    def close(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle:
+            try:
+                _lib.lib().mi355gs_path_destroy(ctypes.c_void_p(handle))
+            except Exception:  # interpreter shutdown
+                pass
+
+    __del__ = close
+
+    def render(self, proj: torch.Tensor, tanfovx: float, tanfovy: float, background: torch.Tensor, sh_degree: int, poses: torch.Tensor,
+               frames: torch.Tensor, counts: torch.Tensor, first: int = 0, n: int | None = None):
+        """Enqueues poses first .. first + n - 1 of `poses` [N,7] into frames[i] (uint8 [N,H,W,3] on the device, or pinned host
+        memory) and counts[i] (int32 [N] on the device).  Nothing is waited for."""
+        dev = self.dev
+        N = int(poses.shape[0])
+        n = N - first if n is None else n
+        if poses.dim() != 2 or poses.shape[1] != 7 or poses.dtype != torch.float32 or poses.device != dev or not poses.is_contiguous():
+            raise ValueError("poses must be contiguous float32 [N,7] on the renderer's device")
+        if first < 0 or n < 0 or first + n > N:
+            raise ValueError(f"frames {first} .. {first + n - 1} of a path of {N} poses")
+        if frames.dtype != torch.uint8 or tuple(frames.shape) != (N, self.H, self.W, 3) or not frames.is_contiguous():
+            raise ValueError(f"frames must be a contiguous uint8 [{N},{self.H},{self.W},3] tensor")
+        if frames.device != dev and not (dev.type == "cuda" and frames.device.type == "cpu" and frames.is_pinned()):
+            raise ValueError("frames must live on the renderer's device or in pinned host memory")
+        if counts.dtype != torch.int32 or counts.numel() != N or counts.device != dev or not counts.is_contiguous():
+            raise ValueError("counts must be contiguous int32 [N] on the renderer's device")
+        proj = proj.to(dev).float().contiguous()
+        bg = background.to(dev).float().contiguous()
+        if proj.numel() != 16 or bg.numel() != 3:
+            raise ValueError("the projection matrix needs 16 floats and the background 3")
+        self._keep = (proj, bg, poses)   # alive until the enqueued work has read them (the caller synchronises per group)
+        with _lib.on_device(dev):
+            _lib.check(_lib.lib().mi355gs_path_render(ctypes.c_void_p(self.handle), _lib.stream_ptr(dev), int(sh_degree), _lib.ptr(proj),
+                                                      float(tanfovx), float(tanfovy), _lib.ptr(bg), _lib.ptr(poses), int(first), int(n),
+                                                      _lib.ptr(frames), _lib.ptr(counts)), "path_render")
+
+
+def _stacked_on_host(tensors) -> torch.Tensor:
+    """The views' per-camera matrices as one host tensor: ONE device-to-host copy for the whole list, not one per view."""
+    return torch.stack([t.detach() for t in tensors]).cpu()
+
+
+def _groups(views):
+    """[(start, stop)] of consecutive views that share the image size, the projection matrix and the field of view"""
+    proj = _stacked_on_host([v.projection_matrix for v in views]).reshape(len(views), -1).tolist() if views else []
+    out, start, key = [], 0, None
+    for i, v in enumerate(views):
+        k = (int(v.image_width), int(v.image_height), tuple(proj[i]), float(v.FoVx), float(v.FoVy))
+        if i and k != key:
+            out.append((start, i))
+            start = i
+        key = k
+    if views:
+        out.append((start, len(views)))
+    return out
+
+
+def _frame_buffer(N, H, W, dev, pinned):
+    if pinned and dev.type == "cuda":   # the conversion kernel stores into it directly: no device-to-host copy of the frames
+        return torch.empty(N, H, W, 3, dtype=torch.uint8, pin_memory=True)
+    return torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+
+
+def render_pose_path(views: List, gaussians, pipe, background, poses: torch.Tensor | None = None, capacity: int | None = None,
+                     pinned: bool = False, scaling_modifier: float = 1.0) -> dict:
+    """The frames of reference render.py:85-93 for a whole camera list, on the device.
+    views: cameras as `load_cameras` returns them; poses [N,7]: the pose of every frame (default: each view's own,
+    get_tensor_from_camera(view.world_view_transform.T) as render.py:86).  Consecutive views with one image size, projection matrix
+    and field of view form a group, rendered through one handle by one library call.
+    capacity: instance capacity of a group's first attempt (default: the exact count at the group's first pose, times
+    BinningPolicy.slack, plus BinningPolicy.pad); after the one read-back of the counts, only the frames that outgrew it are
+    rendered again, through a handle sized from the largest count.
+    Host traffic of a call: the views' projection matrices in one copy and (with default poses) their view matrices in another,
+    both before anything is enqueued; one blocking read of a single count per group when the capacity is probed; the read-back of
+    the counts per group.
+    pinned: the frames are written into pinned host memory by the kernels (returned as a CPU tensor) instead of device memory.
+    -> dict(frames = uint8 [N,H,W,3] (a list of per-group tensors if the groups differ in size), counts = int32 [N] on the host,
+            reruns = frames rendered twice)."""
+    if pipe.convert_SHs_python or pipe.compute_cov3D_python or scaling_modifier != 1.0:
+        raise ValueError("path rendering implements the default pipeline only (SH colours and covariance in the operator, "
+                         "scaling_modifier 1)")
+    views = list(views)
+    if not views:
+        raise ValueError("render_pose_path needs at least one view")
+    dev = gaussians.get_xyz.device
+    N = len(views)
+    if poses is None:
+        w2c = _stacked_on_host([v.world_view_transform for v in views]).transpose(1, 2)
+        poses = torch.stack([get_tensor_from_camera(m) for m in w2c])
+    poses = poses.detach().to(dev).float().reshape(-1, 7).contiguous()
+    if poses.shape[0] != N:
+        raise ValueError(f"{poses.shape[0]} poses for {N} views")
+    D = int(gaussians.active_sh_degree)
+    out_frames, out_counts, reruns = [], [], 0
+    for start, stop in _groups(views):
+        view = views[start]
+        W, H = int(view.image_width), int(view.image_height)
+        proj, tx, ty = view.projection_matrix, math.tan(view.FoVx * 0.5), math.tan(view.FoVy * 0.5)
+        gposes = poses[start:stop].contiguous()
+        n = stop - start
+        frames = _frame_buffer(n, H, W, dev, pinned)
+        counts = torch.zeros(n, dtype=torch.int32, device=dev)
+        cap = capacity
+        if cap is None:   # the exact count of the first pose: one frame through a handle of the smallest size
+            probe = FusedPathRenderer(gaussians, W, H, 1)
+            probe.render(proj, tx, ty, background, D, gposes, frames, counts, 0, 1)
+            cap = int(BinningPolicy.slack * int(counts[0])) + BinningPolicy.pad
+            probe.close()
+        todo = None   # frames to render: all of them first, then those whose count exceeded the capacity
+        while True:
+            renderer = FusedPathRenderer(gaussians, W, H, cap)
+            if todo is None:
+                renderer.render(proj, tx, ty, background, D, gposes, frames, counts)
+            else:
+                for i in todo:
+                    renderer.render(proj, tx, ty, background, D, gposes, frames, counts, i, 1)
+            host_counts = counts.cpu()   # the one read-back of the group (it also orders the frames before the host reads them)
+            renderer.close()
+            todo = [i for i in (range(n) if todo is None else todo) if int(host_counts[i]) > cap]
+            if not todo:
+                break
+            reruns += len(todo)
+            cap = max(int(BinningPolicy.slack * int(host_counts.max())) + BinningPolicy.pad, 2 * cap)
+        out_frames.append(frames)
+        out_counts.append(host_counts)
+    same = all(f.shape[1:] == out_frames[0].shape[1:] for f in out_frames)
+    frames = out_frames[0] if len(out_frames) == 1 else (torch.cat(out_frames) if same else out_frames)
+    return dict(frames=frames, counts=torch.cat(out_counts), reruns=reruns)
+
+
+def _save_png(path: str, hwc: np.ndarray):
+    from PIL import Image
+    Image.fromarray(hwc).save(path)   # (what torchvision.utils.save_image does with the bytes it has quantised)
+
+
+def render_set(model_path, name: str, iteration, views: List, gaussians, pipe, background, fused: bool = True) -> str:
+    """reference render.py:78-97: <model_path>/<name>/ours_<iteration>/renders/{idx:05d}.png for every view and, unless name is
+    "interp", gt/{idx:05d}.png.  fused=False renders frame by frame with render() and quantize_rgb8.  Returns the renders'
+    directory."""
+    views = list(views)
+    base = os.path.join(str(model_path), name, f"ours_{iteration}")
+    render_dir, gts_dir = os.path.join(base, "renders"), os.path.join(base, "gt")
+    os.makedirs(render_dir, exist_ok=True)
+    os.makedirs(gts_dir, exist_ok=True)
+    if fused:
+        frames = render_pose_path(views, gaussians, pipe, background)["frames"]
+        frames = [f.cpu().numpy() for f in frames] if isinstance(frames, list) else [frames.cpu().numpy()]
+        frames = [f for group in frames for f in group]
+    else:
+        frames = []
+        with torch.no_grad():
+            for view in views:
+                pose = get_tensor_from_camera(view.world_view_transform.transpose(0, 1).cpu()).to(gaussians.get_xyz.device)
+                frames.append(quantize_rgb8(render(view, gaussians, pipe, background, camera_pose=pose)["render"]).cpu().numpy())
+    for idx, (view, frame) in enumerate(zip(views, frames)):
+        _save_png(os.path.join(render_dir, f"{idx:05d}.png"), frame)
+        if name != "interp":
+            gt = view.original_image[0:3].to(gaussians.get_xyz.device).float().contiguous()
+            _save_png(os.path.join(gts_dir, f"{idx:05d}.png"), quantize_rgb8(gt).cpu().numpy())
+    return render_dir
+
+
+def images_to_video(image_folder: str, output_video_path: str, fps: int = 30) -> bool:
+    """reference render.py:59-76, if imageio is installed; False (and nothing written) if it is not."""
+    try:
+        import imageio
+    except ImportError:
+        return False
+    images = [imageio.imread(os.path.join(image_folder, f)) for f in sorted(os.listdir(image_folder))
+              if f.endswith((".png", ".jpg", ".jpeg", ".JPG", ".PNG"))]
+    imageio.mimwrite(output_video_path, images, fps=fps)
+    return True
+
+
+def render_interpolated(model_path, iteration, n_views: int, train_cameras: List, gaussians, pipe, background, fused: bool = True) -> str:
+    """The `--infer_video` stage (reference render.py:233-248): pose_interpolated.npy from the optimised poses, the training cameras
+    repeated along it, every pose rendered to interp/ours_<iteration>/renders/, and interp_<n_views>_view.mp4 beside that
+    directory if imageio is installed (otherwise a message says that the video was skipped).  Returns the frame directory."""
+    pose_file = save_interpolate_pose(model_path, iteration, n_views)
+    cams = [copy.copy(c) for c in train_cameras]
+    for c in cams:   # load_cameras copies every camera it repeats along the path; the "interp" set writes no ground truth
+        c.original_image = None
+    views = load_cameras(np.load(pose_file), cams)
+    render_dir = render_set(model_path, "interp", iteration, views, gaussians, pipe, background, fused=fused)
+    video = os.path.join(str(model_path), "interp", f"ours_{iteration}", f"interp_{n_views}_view.mp4")
+    if images_to_video(render_dir, video):
+        print(f"wrote {len(views)} frames and {video}")
+    else:
+        print(f"wrote {len(views)} frames to {render_dir}; the video was skipped (imageio is not installed)")
+    return render_dir
