@@ -14,9 +14,9 @@
  *   - state: the per-operator entry points keep nothing between calls.  Exceptions, all host-side and documented at their
  *     declarations: the opt-in event timing (mi355gs_profile_*), the process-wide tuning knob mi355gs_tune_min_units, and
  *     the trainer handle.  Threading: calls may be made from any host thread, one call at a time per stream; the
- *     composite entry points (mi355gs_posed_*, mi355gs_trainer_*) pass per-call context to the operator entry points
- *     they re-enter through a THREAD-LOCAL hook block (csrc/common.h, GsFusedStepHooks), set and cleared inside the call —
- *     so concurrent calls from different threads do not see each other's context, and nothing of it survives the call.
+ *     composite entry points (mi355gs_posed_*, mi355gs_trainer_*, mi355gs_tracker_*, mi355gs_path_*) hand their per-call
+ *     context to the shared frame functions as arguments (csrc/common.h, GsFrameCtx) — no call leaves anything behind in
+ *     the library, on any thread.
  *
  * Each entry point names the reference interface it replaces. The reference's three native
  * operators are un-vendored git submodules (reference .gitmodules:1-12), so the citations are

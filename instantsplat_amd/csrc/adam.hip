@@ -198,15 +198,16 @@ __global__ __launch_bounds__(256) void k_adam_multi(MultiAdamArgs a, const float
 
 }  // namespace
 
-extern "C" int mi355gs_adam_multi_step(void* stream_, int ntensors, const int64_t* numel, const int32_t* row, float* const* params,
-                                       const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                       const float* const* per_point_lr, const float* lr, float beta1, float beta2, float eps,
-                                       const int32_t* step, float* scratch, const float* gate, const int32_t* gate_index,
-                                       uint32_t* live, uint32_t seq) {
-  GS_RANGE();
-  hipStream_t stream = (hipStream_t)stream_;
+// Three gate modes: the caller's `gate` / `gate_index` (tensors without a flag are summed by a launch of their own or gated by
+// the workgroup that owns them), the fused step's flags in `scratch` (`fused`, which excludes `gate`), or a sum-of-squares pass
+// over every gradient.
+int gs_adam_multi(hipStream_t stream, int ntensors, const int64_t* numel, const int32_t* row, float* const* params,
+                  const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const float* const* per_point_lr,
+                  const float* lr, float beta1, float beta2, float eps, const int32_t* step, float* scratch, const float* gate,
+                  const int32_t* gate_index, uint32_t* live, uint32_t seq, const GsAdamFused* fused) {
+  GsRange range("mi355gs_adam_multi_step");
   const int debug = 0;
-  if (ntensors < 0 || ntensors > MT_MAX || (gate && !gate_index)) return MI355GS_EINVAL;
+  if (ntensors < 0 || ntensors > MT_MAX || (gate && !gate_index) || (fused && (gate || !scratch))) return MI355GS_EINVAL;
   if (ntensors == 0) return MI355GS_OK;
   if (!numel || !row || !params || !grads || !exp_avg || !exp_avg_sq || !per_point_lr || !lr || !step) return MI355GS_EINVAL;
   MultiAdamArgs a;
@@ -237,9 +238,9 @@ extern "C" int mi355gs_adam_multi_step(void* stream_, int ntensors, const int64_
   a.first_block[MT_MAX] = blocks;
   a.live = nullptr; a.seq = 0; a.commit_count = nullptr; a.commit_capacity = 0; a.commit_poison = nullptr;
   if (blocks == 0) return MI355GS_OK;
-  if (!gate && g_fused.gate == scratch) {
-    a.live = g_fused.adam_live; a.seq = g_fused.adam_seq;
-    a.commit_count = g_fused.commit_count; a.commit_capacity = g_fused.commit_capacity; a.commit_poison = g_fused.commit_poison;
+  if (fused) {
+    a.live = fused->live; a.seq = fused->seq;
+    a.commit_count = fused->commit_count; a.commit_capacity = fused->commit_capacity; a.commit_poison = fused->commit_poison;
   } else if (live && seq != 0u) {
     a.live = live; a.seq = seq;   // the caller's own memory of gated-off tensors (include/mi355gs.h)
   }
@@ -276,7 +277,7 @@ extern "C" int mi355gs_adam_multi_step(void* stream_, int ntensors, const int64_
         GS_CHECK_LAUNCH("adam_sumsq");
       }
     }
-  } else if (g_fused.gate == scratch) {
+  } else if (fused) {
     // fused train step: the gate flags were written by the kernels that produced the gradients
     a.gate = scratch;
     for (int t = 0; t < ntensors; ++t) a.gidx[t] = t;
@@ -290,6 +291,15 @@ extern "C" int mi355gs_adam_multi_step(void* stream_, int ntensors, const int64_
   hipLaunchKernelGGL(k_adam_multi, dim3(blocks), dim3(256), 0, stream, a, (const float*)scratch, beta1, beta2, eps);
   GS_CHECK_LAUNCH("adam_multi");
   return MI355GS_OK;
+}
+
+extern "C" int mi355gs_adam_multi_step(void* stream, int ntensors, const int64_t* numel, const int32_t* row, float* const* params,
+                                       const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                       const float* const* per_point_lr, const float* lr, float beta1, float beta2, float eps,
+                                       const int32_t* step, float* scratch, const float* gate, const int32_t* gate_index,
+                                       uint32_t* live, uint32_t seq) {
+  return gs_adam_multi((hipStream_t)stream, ntensors, numel, row, params, grads, exp_avg, exp_avg_sq, per_point_lr, lr, beta1, beta2, eps,
+                       step, scratch, gate, gate_index, live, seq, nullptr);
 }
 
 extern "C" int mi355gs_adam_step(void* stream_, int64_t n, int row, float* param, const float* grad, float* exp_avg,

@@ -8,13 +8,13 @@
 // launchers implemented next to their kernels
 int gs_launch_preprocess_fwd(hipStream_t, int, int, int, const float*, const float*, const float*, const float*, const float*, const float*,
                              const float*, const float*, const CamParams&, int32_t*, GsRec*, float*, uint2*, uint8_t*, float*, uint8_t*,
-                             const GsPrologue&);
+                             const GsPosed&, const GsPrologue&);
 int gs_launch_count_tiles(hipStream_t, int, int, int, const uint2*, uint32_t*, uint32_t*, uint32_t*);
 int gs_launch_preprocess_bwd(hipStream_t, int, int, int, const float*, const float*, const float*, const float*, const float*, int, int,
                              const CamParams&, const int32_t*, const GsRec*, const float*, const uint8_t*, const GsGrad*, float*, float*,
-                             float*, float*, float*, float*, float*, float*, float*, float*, float*);
+                             float*, float*, float*, float*, float*, float*, float*, const GsPosed&, float*, bool);
 int gs_launch_mark_visible(hipStream_t, int, const float*, const float*, uint8_t*);
-int gs_launch_scan_tiles(hipStream_t, int, const uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*);
+int gs_launch_scan_tiles(hipStream_t, int, const uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, int);
 int gs_launch_binning(hipStream_t, int, int, int, const float*, const uint2*, const uint32_t*, uint32_t*, uint64_t*, uint32_t*, uint32_t,
                       const uint32_t*, const uint32_t*, const uint32_t*);
 int gs_launch_composite_fwd(hipStream_t, int, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
@@ -59,8 +59,6 @@ GsProfScope::GsProfScope(int kind, hipStream_t stream) : s(stream) {
 GsProfScope::~GsProfScope() { if (active) (void)hipEventRecord(stop, s); }
 typedef GsProfScope ProfScope;
 
-thread_local GsFusedStepHooks g_fused;
-
 // ---- roctx ranges (mi355gs_profile_ranges): the marker library is opened at run time, on request
 bool g_ranges_on = false;
 thread_local bool g_krange_open = false;
@@ -96,9 +94,7 @@ void gs_log_error(const char* where, const char* what) { fprintf(stderr, "[mi355
 
 static int g_scale_grad_exact = 0;   // mi355gs_tune_scale_grad
 static int g_deterministic = 0;      // mi355gs_tune_deterministic
-thread_local int g_deterministic_pinned = -1;   // a trainer handle's snapshot, in force for the duration of its calls
-int gs_deterministic() { return g_deterministic_pinned >= 0 ? g_deterministic_pinned : g_deterministic; }
-void gs_pin_deterministic(int v) { g_deterministic_pinned = v; }
+GsKnobs gs_knobs() { return GsKnobs{gs_min_units(), g_deterministic}; }
 
 static CamParams make_cam(const float* view, const float* proj, const float* campos, float tanfovx, float tanfovy,
                           float scale_modifier, int W, int H) {
@@ -123,72 +119,52 @@ __global__ void k_view_consts(float* consts) {
   else if (i < 19) consts[i] = 0.f;                   // camera position
 }
 }  // namespace
-void gs_launch_view_consts(hipStream_t stream, float* consts) {
+int gs_write_view_consts(hipStream_t stream, float* consts, const char* name) {
+  const int debug = 0;
+  GS_KRANGE(name);
   hipLaunchKernelGGL(k_view_consts, dim3(1), dim3(64), 0, stream, consts);
+  GS_CHECK_LAUNCH(name);
+  return MI355GS_OK;
 }
 
-extern "C" {
+// ---- one frame, explicitly (common.h): the bodies of the public mi355gs_raster_* operators below.  Each validates what it is
+// handed, so that mi355gs_posed_* and the handles answer a bad argument as the operators do, and opens the range the operator
+// is known by in a marker trace.
 
-int mi355gs_abi_version(void) { return MI355GS_ABI_VERSION; }
-
-const char* mi355gs_error_string(int code) {
-  switch (code) {
-    case MI355GS_OK: return "ok";
-    case MI355GS_EINVAL: return "invalid argument";
-    case MI355GS_ELAUNCH: return "HIP launch or runtime failure";
-    case MI355GS_EOVERFLOW: return "instance capacity exceeded";
-    default: return "unknown error";
-  }
-}
-
-size_t mi355gs_raster_geom_bytes(int P) { return GeomLayout(P).total; }
-size_t mi355gs_raster_tiles_bytes(int W, int H) { return (W > 0 && H > 0) ? TilesLayout(W, H).total : 0; }
-size_t mi355gs_raster_binning_bytes(int64_t n, int W, int H) {
-  if (W <= 0 || H <= 0) return 0;
-  return BinningLayout(n, TilesLayout(W, H).T).total;
-}
-size_t mi355gs_raster_grad_gate_offset(int P) { return gs_align((size_t)(P > 0 ? P : 1) * sizeof(GsGrad)); }
-size_t mi355gs_raster_grad_scratch_bytes(int P) {
-  return mi355gs_raster_grad_gate_offset(P) + 256 + (gs_deterministic() ? DetScratchLayout(P).total : 0);
-}
-
-int mi355gs_raster_forward_preprocess(void* stream_, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
-                                      const float* shs_rest, const float* colors_precomp, const float* opacities, const float* scales,
-                                      float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                                      const float* viewmatrix, const float* projmatrix, const float* campos, float tanfovx,
-                                      float tanfovy, int prefiltered, int32_t* radii, void* geom, void* tiles,
-                                      int32_t* num_rendered, uint8_t* visible, void* grad_scratch, int debug) {
-  GS_RANGE();
-  (void)prefiltered;  // as in the reference operator it only affects an internal consistency check
-  hipStream_t stream = (hipStream_t)stream_;
+int gs_frame_project(hipStream_t stream, const GsScene& sc, const GsView& vw, const GsFrameBufs& fb, const GsFrameCtx& cx,
+                     int32_t* num_rendered, uint8_t* visible, int debug) {
+  GsRange range("mi355gs_raster_forward_preprocess");
+  const int P = sc.P, D = sc.D, M = sc.M, W = vw.W, H = vw.H;
   if (P < 0 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE || D < 0 || D > 3) return MI355GS_EINVAL;
-  if (!geom || !tiles || !num_rendered || !viewmatrix || !projmatrix || !campos) return MI355GS_EINVAL;
-  if (P > 0 && (!means3D || !opacities || !radii)) return MI355GS_EINVAL;
-  if (P > 0 && ((shs == nullptr) == (colors_precomp == nullptr))) return MI355GS_EINVAL;
-  if (P > 0 && shs && M < (D + 1) * (D + 1)) return MI355GS_EINVAL;
-  if (shs_rest && (!shs || M < 2)) return MI355GS_EINVAL;
-  if (P > 0 && !cov3D_precomp && (!scales || !rotations)) return MI355GS_EINVAL;
+  if (!fb.geom || !fb.tiles || !num_rendered || !vw.view || !vw.proj || !vw.campos) return MI355GS_EINVAL;
+  if (P > 0 && (!sc.means3D || !sc.opacities || !fb.radii)) return MI355GS_EINVAL;
+  if (P > 0 && ((sc.shs == nullptr) == (sc.colors_precomp == nullptr))) return MI355GS_EINVAL;
+  if (P > 0 && sc.shs && M < (D + 1) * (D + 1)) return MI355GS_EINVAL;
+  if (sc.shs_rest && (!sc.shs || M < 2)) return MI355GS_EINVAL;
+  if (P > 0 && !sc.cov3D_precomp && (!sc.scales || !sc.rotations)) return MI355GS_EINVAL;
   const GeomLayout gl(P);
   const TilesLayout tl(W, H);
-  char* g = (char*)geom;
-  char* t = (char*)tiles;
-  // The frame's accumulators are cleared by the projection kernel on its way (the one-call step hands over its own list): the
+  char* g = (char*)fb.geom;
+  char* t = (char*)fb.tiles;
+  // The frame's accumulators are cleared by the projection kernel on its way (a fused caller hands over its own list): the
   // per-tile count + cursor words (adjacent), and — if the caller already holds the buffer its backward will use — the moment
   // records with the gate flags behind them.  No Gaussians, no kernel: memsets then.
-  GsPrologue pro = g_fused.prologue;
-  if (!g_fused.skip_memsets) {
-    pro = GsPrologue();
+  GsPrologue pro;
+  if (cx.prologue) {
+    pro = *cx.prologue;
+  } else {
     pro.tile_counters = (uint32_t*)(t + tl.count); pro.n_counters = (int)((tl.start - tl.count) / 4);
-    if (grad_scratch) { pro.grad_records = (float4*)grad_scratch; pro.n_vec = mi355gs_raster_grad_gate_offset(P) / 16 + 2; }
+    if (fb.grad_scratch) { pro.grad_records = (float4*)fb.grad_scratch; pro.n_vec = gs_grad_gate_offset(P) / 16 + 2; }
     if (P <= 0) {
       if (hipMemsetAsync(t + tl.count, 0, tl.start - tl.count, stream) != hipSuccess) return MI355GS_ELAUNCH;
-      if (grad_scratch && hipMemsetAsync(grad_scratch, 0, mi355gs_raster_grad_gate_offset(P) + 32, stream) != hipSuccess) return MI355GS_ELAUNCH;
+      if (fb.grad_scratch && hipMemsetAsync(fb.grad_scratch, 0, gs_grad_gate_offset(P) + 32, stream) != hipSuccess) return MI355GS_ELAUNCH;
     }
   }
-  const CamParams cp = make_cam(viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier, W, H);
+  const CamParams cp = make_cam(vw.view, vw.proj, vw.campos, vw.tanfovx, vw.tanfovy, sc.scale_modifier, W, H);
   GS_KRANGE("preprocess_fwd");
-  gs_launch_preprocess_fwd(stream, P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, rotations, cov3D_precomp, cp, radii,
-                           (GsRec*)(g + gl.rec), (float*)(g + gl.cov3D), (uint2*)(g + gl.rect), (uint8_t*)(g + gl.clamped), (float*)(g + gl.depth), visible, pro);
+  gs_launch_preprocess_fwd(stream, P, D, M, sc.means3D, sc.shs, sc.shs_rest, sc.colors_precomp, sc.opacities, sc.scales, sc.rotations,
+                           sc.cov3D_precomp, cp, fb.radii, (GsRec*)(g + gl.rec), (float*)(g + gl.cov3D), (uint2*)(g + gl.rect),
+                           (uint8_t*)(g + gl.clamped), (float*)(g + gl.depth), visible, cx.posed, pro);
   GS_CHECK_LAUNCH("preprocess_fwd");
   GS_KRANGE("count_tiles");
   gs_launch_count_tiles(stream, P, tl.T, tl.gx, (const uint2*)(g + gl.rect), (uint32_t*)(t + tl.count), (uint32_t*)(g + gl.bin_entries),
@@ -196,25 +172,27 @@ int mi355gs_raster_forward_preprocess(void* stream_, int P, int D, int M, int W,
   GS_CHECK_LAUNCH("count_tiles");
   GS_KRANGE("scan_tiles");
   gs_launch_scan_tiles(stream, tl.T, (const uint32_t*)(t + tl.count), (uint32_t*)(t + tl.start), num_rendered,
-                       (uint32_t*)(t + tl.order), (uint32_t*)(t + tl.meta), (uint32_t*)(t + tl.seg_first), (uint32_t*)(t + tl.part_first));
+                       (uint32_t*)(t + tl.order), (uint32_t*)(t + tl.meta), (uint32_t*)(t + tl.seg_first), (uint32_t*)(t + tl.part_first),
+                       fb.knobs.min_units);
   GS_CHECK_LAUNCH("scan_tiles");
   return MI355GS_OK;
 }
 
 // Stage 2 of the forward in its two forms: `train` leaves the backward's work units, boundary records, hit masks and quadrant
 // maxima in `binning` / `tiles`; render-only has a `binning` of keys + lists only and writes the image and the per-pixel state.
-static int forward_stage2(void* stream_, int P, int W, int H, int64_t capacity, const float* bg, const void* geom, void* tiles,
-                          void* binning, float* out_color, int debug, bool train) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (P < 0 || W <= 0 || H <= 0 || !geom || !tiles || !bg || !out_color) return MI355GS_EINVAL;
-  const uint32_t cap = clamp_capacity(capacity);
-  if (cap > 0 && !binning) return MI355GS_EINVAL;
+int gs_frame_render(hipStream_t stream, int P, const GsView& vw, const GsFrameBufs& fb, const float* bg, float* out_color, bool train,
+                    int debug) {
+  GsRange range(train ? "mi355gs_raster_forward_render" : "mi355gs_raster_forward_render_only");
+  const int W = vw.W, H = vw.H;
+  if (P < 0 || W <= 0 || H <= 0 || !fb.geom || !fb.tiles || !bg || !out_color) return MI355GS_EINVAL;
+  const uint32_t cap = clamp_capacity(fb.capacity);
+  if (cap > 0 && !fb.binning) return MI355GS_EINVAL;
   const GeomLayout gl(P);
   const TilesLayout tl(W, H);
-  const BinningLayout bl(capacity, tl.T);   // (keys and list come first in it: the render-only buffer is its head)
-  const char* g = (const char*)geom;
-  char* t = (char*)tiles;
-  char* b = (char*)binning;
+  const BinningLayout bl(fb.capacity, tl.T, fb.knobs);   // (keys and list come first in it: the render-only buffer is its head)
+  const char* g = (const char*)fb.geom;
+  char* t = (char*)fb.tiles;
+  char* b = (char*)fb.binning;
   GS_KRANGE("binning");
   gs_launch_binning(stream, P, tl.T, tl.gx, (const float*)(g + gl.depth), (const uint2*)(g + gl.rect),
                     (const uint32_t*)(t + tl.start), (uint32_t*)(t + tl.cursor), (uint64_t*)(b + bl.keys),
@@ -235,72 +213,51 @@ static int forward_stage2(void* stream_, int P, int W, int H, int64_t capacity, 
   return MI355GS_OK;
 }
 
-int mi355gs_raster_forward_render(void* stream, int P, int W, int H, int64_t capacity, const float* bg, const void* geom,
-                                  void* tiles, void* binning, float* out_color, int debug) {
-  GS_RANGE();
-  return forward_stage2(stream, P, W, H, capacity, bg, geom, tiles, binning, out_color, debug, true);
-}
-
-size_t mi355gs_raster_binning_bytes_render_only(int64_t n, int W, int H) {
-  if (W <= 0 || H <= 0) return 0;
-  return BinningLayout(n, TilesLayout(W, H).T).unit_tile;   // keys + list: everything in front of the backward's tables
-}
-
-int mi355gs_raster_forward_render_only(void* stream, int P, int W, int H, int64_t capacity, const float* bg, const void* geom,
-                                       void* tiles, void* binning, float* out_color, int debug) {
-  GS_RANGE();
-  return forward_stage2(stream, P, W, H, capacity, bg, geom, tiles, binning, out_color, debug, false);
-}
-
-int mi355gs_raster_backward(void* stream_, int P, int D, int M, int W, int H, const float* bg, const float* means3D,
-                            const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities, const float* scales,
-                            float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                            const float* projmatrix, const float* campos, float tanfovx, float tanfovy, const void* geom,
-                            void* tiles, const void* binning, int64_t capacity, const int32_t* radii, const float* out_color,
-                            const float* dL_dpix, void* grad_scratch, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs,
-                            float* dL_dshs_rest, float* dL_dcolors, float* dL_dopacities, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                            int grad_scratch_is_clear, int debug) {
-  GS_RANGE();
-  (void)opacities; (void)colors_precomp;
-  hipStream_t stream = (hipStream_t)stream_;
+int gs_frame_backward(hipStream_t stream, const GsScene& sc, const GsView& vw, const GsFrameBufs& fb, const GsFrameCtx& cx,
+                      const float* bg, const float* out_color, const float* dL_dpix, const GsGradOut& o, bool grad_scratch_is_clear,
+                      int debug) {
+  GsRange range("mi355gs_raster_backward");
+  const int P = sc.P, D = sc.D, W = vw.W, H = vw.H;
   if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3) return MI355GS_EINVAL;
-  if (!geom || !tiles || !dL_dpix || !out_color || !grad_scratch || !bg || !viewmatrix || !projmatrix || !campos) return MI355GS_EINVAL;
-  // pose-only (pose tracking, see GsFusedStepHooks::pose_only): no output is stored, so none is required
-  const bool outs = !(g_fused.pose_only && g_fused.posed.pose);
-  if (P > 0 && (!means3D || !radii || (outs && (!dL_dmeans3D || !dL_dmeans2D || !dL_dopacities)))) return MI355GS_EINVAL;
-  const int use_shs = shs != nullptr, use_cov = cov3D_precomp != nullptr;
-  if (P > 0 && outs && use_shs && !dL_dshs) return MI355GS_EINVAL;
-  if (shs_rest && !use_shs) return MI355GS_EINVAL;
-  if (P > 0 && outs && !use_shs && !dL_dcolors) return MI355GS_EINVAL;
-  if (P > 0 && !use_cov && (!scales || !rotations || (outs && (!dL_dscales || !dL_drotations)))) return MI355GS_EINVAL;
-  if (P > 0 && outs && use_cov && !dL_dcov3D) return MI355GS_EINVAL;
+  if (!fb.geom || !fb.tiles || !dL_dpix || !out_color || !fb.grad_scratch || !bg || !vw.view || !vw.proj || !vw.campos) return MI355GS_EINVAL;
+  const bool outs = !(cx.pose_only && cx.posed.pose);   // pose-only stores no output, so none is required
+  if (P > 0 && (!sc.means3D || !fb.radii || (outs && (!o.means3D || !o.means2D || !o.opacities)))) return MI355GS_EINVAL;
+  const int use_shs = sc.shs != nullptr, use_cov = sc.cov3D_precomp != nullptr;
+  if (P > 0 && outs && use_shs && !o.shs) return MI355GS_EINVAL;
+  if (sc.shs_rest && !use_shs) return MI355GS_EINVAL;
+  if (P > 0 && outs && !use_shs && !o.colors) return MI355GS_EINVAL;
+  if (P > 0 && !use_cov && (!sc.scales || !sc.rotations || (outs && (!o.scales || !o.rotations)))) return MI355GS_EINVAL;
+  if (P > 0 && outs && use_cov && !o.cov3D) return MI355GS_EINVAL;
   if (P == 0) return MI355GS_OK;
-  const uint32_t cap = clamp_capacity(capacity);
-  if (cap > 0 && !binning) return MI355GS_EINVAL;
+  const uint32_t cap = clamp_capacity(fb.capacity);
+  if (cap > 0 && !fb.binning) return MI355GS_EINVAL;
   const GeomLayout gl(P);
   const TilesLayout tl(W, H);
-  const BinningLayout bl(capacity, tl.T);
-  const char* g = (const char*)geom;
-  const char* t = (const char*)tiles;
-  const char* b = (const char*)binning;
-  GsGrad* grads = (GsGrad*)grad_scratch;
+  const BinningLayout bl(fb.capacity, tl.T, fb.knobs);
+  const char* g = (const char*)fb.geom;
+  const char* t = (const char*)fb.tiles;
+  char* b = (char*)fb.binning;
+  GsGrad* grads = (GsGrad*)fb.grad_scratch;
   // (with gate_tail the eight gate flags behind the records are cleared by the same memset)
-  const size_t clear_bytes = g_fused.gate_tail ? mi355gs_raster_grad_gate_offset(P) + 8 * sizeof(float) : (size_t)P * sizeof(GsGrad);
-  if (!g_fused.skip_memsets && !grad_scratch_is_clear && hipMemsetAsync(grads, 0, clear_bytes, stream) != hipSuccess) return MI355GS_ELAUNCH;
+  const size_t clear_bytes = cx.gate_tail ? gs_grad_gate_offset(P) + 8 * sizeof(float) : (size_t)P * sizeof(GsGrad);
+  if (!cx.prologue && !grad_scratch_is_clear && hipMemsetAsync(grads, 0, clear_bytes, stream) != hipSuccess) return MI355GS_ELAUNCH;
   if (cap > 0) {
     // deterministic mode: every instance's moments go to a row of their own (binning: det_rows / det_rowidx) and are summed per
     // Gaussian in rectangle order by k_det_gather, which writes every record — instead of meeting in float atomics
-    const bool det = gs_deterministic() != 0;
-    char* det_scratch = (char*)grad_scratch + mi355gs_raster_grad_gate_offset(P) + 256;
-    uint32_t* rowidx = det ? (uint32_t*)(const_cast<char*>(b) + bl.det_rowidx) : nullptr;
-    float* rows = det ? (float*)(const_cast<char*>(b) + bl.det_rows) : nullptr;
+    const bool det = fb.knobs.det != 0;
+    char* det_scratch = (char*)fb.grad_scratch + gs_grad_gate_offset(P) + 256;
+    uint32_t* rowidx = det ? (uint32_t*)(b + bl.det_rowidx) : nullptr;
+    float* rows = det ? (float*)(b + bl.det_rows) : nullptr;
     if (det) {
-      if (gs_launch_det_prepare(stream, P, tl.T, tl.gx, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list),
-                                (const uint2*)(g + gl.rect), det_scratch, rowidx, rows) != 0) return MI355GS_ELAUNCH;
+      GS_KRANGE("det_prepare");
+      const int rc = gs_launch_det_prepare(stream, P, tl.T, tl.gx, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list),
+                                           (const uint2*)(g + gl.rect), det_scratch, rowidx, rows);
       GS_CHECK_LAUNCH("det_prepare");
+      if (rc != 0) return MI355GS_ELAUNCH;
     }
     {
       ProfScope prof(1, stream);
+      GS_KRANGE("composite_bwd");
       gs_launch_composite_bwd(stream, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list),
                               (const GsRec*)(g + gl.rec), bg, (const float*)(t + tl.final_T), (const uint32_t*)(t + tl.n_contrib),
                               dL_dpix, grads, out_color, (const uint4*)(b + bl.unit_tile),
@@ -308,19 +265,83 @@ int mi355gs_raster_backward(void* stream_, int P, int D, int M, int W, int H, co
                               (const unsigned long long*)(b + bl.hitmask), bl.max_chunks, (const uint32_t*)(t + tl.qmax),
                               det ? nullptr : g_prof.work_counters, rowidx, rows);
     }
-    GS_KRANGE("composite_bwd");
-    if (det) gs_launch_det_gather(stream, P, cap, det_scratch, rows, grads);
     GS_CHECK_LAUNCH("composite_bwd");
+    if (det) {
+      GS_KRANGE("det_gather");
+      gs_launch_det_gather(stream, P, cap, det_scratch, rows, grads);
+      GS_CHECK_LAUNCH("det_gather");
+    }
   }
-  const CamParams cp = make_cam(viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier, W, H);
+  const CamParams cp = make_cam(vw.view, vw.proj, vw.campos, vw.tanfovx, vw.tanfovy, sc.scale_modifier, W, H);
   GS_KRANGE("preprocess_bwd");
-  gs_launch_preprocess_bwd(stream, P, D, M, means3D, shs, shs_rest, scales, rotations, use_shs, use_cov, cp, radii,
-                           (const GsRec*)(g + gl.rec), (const float*)(g + gl.cov3D), (const uint8_t*)(g + gl.clamped), grads, dL_dmeans3D, dL_dmeans2D,
-                           dL_dshs, dL_dshs_rest, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D,
-                           (g_fused.gate && g_fused.gate_sh >= 0) ? g_fused.gate + g_fused.gate_sh : nullptr,
-                           (g_fused.gate && g_fused.gate_sh_rest >= 0) ? g_fused.gate + g_fused.gate_sh_rest : nullptr);
+  gs_launch_preprocess_bwd(stream, P, D, sc.M, sc.means3D, sc.shs, sc.shs_rest, sc.scales, sc.rotations, use_shs, use_cov, cp, fb.radii,
+                           (const GsRec*)(g + gl.rec), (const float*)(g + gl.cov3D), (const uint8_t*)(g + gl.clamped), grads, o.means3D,
+                           o.means2D, o.shs, o.shs_rest, o.colors, o.opacities, o.scales, o.rotations, o.cov3D, cx.posed, cx.gate,
+                           cx.pose_only);
   GS_CHECK_LAUNCH("preprocess_bwd");
   return MI355GS_OK;
+}
+
+extern "C" {
+
+int mi355gs_abi_version(void) { return MI355GS_ABI_VERSION; }
+
+const char* mi355gs_error_string(int code) {
+  switch (code) {
+    case MI355GS_OK: return "ok";
+    case MI355GS_EINVAL: return "invalid argument";
+    case MI355GS_ELAUNCH: return "HIP launch or runtime failure";
+    case MI355GS_EOVERFLOW: return "instance capacity exceeded";
+    default: return "unknown error";
+  }
+}
+
+// the size queries answer for the knobs as they stand now
+size_t mi355gs_raster_geom_bytes(int P) { return GeomLayout(P).total; }
+size_t mi355gs_raster_tiles_bytes(int W, int H) { return (W > 0 && H > 0) ? TilesLayout(W, H).total : 0; }
+size_t mi355gs_raster_binning_bytes(int64_t n, int W, int H) { return (W > 0 && H > 0) ? gs_binning_bytes(n, W, H, gs_knobs(), true) : 0; }
+size_t mi355gs_raster_binning_bytes_render_only(int64_t n, int W, int H) { return (W > 0 && H > 0) ? gs_binning_bytes(n, W, H, gs_knobs(), false) : 0; }
+size_t mi355gs_raster_grad_gate_offset(int P) { return gs_grad_gate_offset(P); }
+size_t mi355gs_raster_grad_scratch_bytes(int P) { return gs_grad_scratch_bytes(P, g_deterministic); }
+
+// ---- the stateless operators: the frame functions with the current knobs and no context
+int mi355gs_raster_forward_preprocess(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
+                                      const float* shs_rest, const float* colors_precomp, const float* opacities, const float* scales,
+                                      float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                      const float* viewmatrix, const float* projmatrix, const float* campos, float tanfovx,
+                                      float tanfovy, int prefiltered, int32_t* radii, void* geom, void* tiles,
+                                      int32_t* num_rendered, uint8_t* visible, void* grad_scratch, int debug) {
+  (void)prefiltered;  // as in the reference operator it only affects an internal consistency check
+  return gs_frame_project((hipStream_t)stream, {P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier},
+                          {W, H, viewmatrix, projmatrix, campos, tanfovx, tanfovy}, {geom, tiles, nullptr, 0, radii, grad_scratch, gs_knobs()},
+                          GsFrameCtx(), num_rendered, visible, debug);
+}
+
+int mi355gs_raster_forward_render(void* stream, int P, int W, int H, int64_t capacity, const float* bg, const void* geom,
+                                  void* tiles, void* binning, float* out_color, int debug) {
+  return gs_frame_render((hipStream_t)stream, P, {W, H}, {const_cast<void*>(geom), tiles, binning, capacity, nullptr, nullptr, gs_knobs()}, bg,
+                         out_color, true, debug);
+}
+
+int mi355gs_raster_forward_render_only(void* stream, int P, int W, int H, int64_t capacity, const float* bg, const void* geom,
+                                       void* tiles, void* binning, float* out_color, int debug) {
+  return gs_frame_render((hipStream_t)stream, P, {W, H}, {const_cast<void*>(geom), tiles, binning, capacity, nullptr, nullptr, gs_knobs()}, bg,
+                         out_color, false, debug);
+}
+
+int mi355gs_raster_backward(void* stream, int P, int D, int M, int W, int H, const float* bg, const float* means3D,
+                            const float* shs, const float* shs_rest, const float* colors_precomp, const float* opacities, const float* scales,
+                            float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                            const float* projmatrix, const float* campos, float tanfovx, float tanfovy, const void* geom,
+                            void* tiles, const void* binning, int64_t capacity, const int32_t* radii, const float* out_color,
+                            const float* dL_dpix, void* grad_scratch, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs,
+                            float* dL_dshs_rest, float* dL_dcolors, float* dL_dopacities, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                            int grad_scratch_is_clear, int debug) {
+  const GsGradOut o = {dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dshs_rest, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D};
+  return gs_frame_backward((hipStream_t)stream, {P, D, M, means3D, shs, shs_rest, colors_precomp, opacities, scales, rotations, cov3D_precomp, scale_modifier},
+                           {W, H, viewmatrix, projmatrix, campos, tanfovx, tanfovy},
+                           {const_cast<void*>(geom), tiles, const_cast<void*>(binning), capacity, const_cast<int32_t*>(radii), grad_scratch, gs_knobs()},
+                           GsFrameCtx(), bg, out_color, dL_dpix, o, grad_scratch_is_clear != 0, debug);
 }
 
 int mi355gs_tune_deterministic(int on) {

@@ -46,8 +46,9 @@ struct GsCarver {
   }
 };
 // The device constants InstantSplat's render() hands the operator (reference gaussian_renderer/__init__.py:55-59), written by
-// one tiny launch (api.hip): consts[0..15] = the identity view matrix, consts[16..18] = the camera position 0.
-void gs_launch_view_consts(hipStream_t stream, float* consts);
+// one tiny launch (api.hip): consts[0..15] = the identity view matrix, consts[16..18] = the camera position 0.  `name`: the
+// launch's range in a marker trace.
+int gs_write_view_consts(hipStream_t stream, float* consts, const char* name);
 
 // Binning (binning.hip): a workgroup counts / scatters GS_BIN_CHUNK consecutive Gaussians; the count kernel leaves each
 // workgroup's touched tiles as up to GS_BIN_ENTRIES packed (tile | count << 16) words for the scatter kernel of the same frame.
@@ -83,8 +84,13 @@ __host__ __device__ inline int gs_unit_level_for(long long instances, long long 
 // Deterministic-backward mode (mi355gs_tune_deterministic, composite.hip): the moments of every (Gaussian, tile) instance go to a
 // row of their own and are summed per Gaussian in tile order instead of meeting in float atomics.  It enters the layouts below
 // (rows + row indices per instance in `binning`, the per-Gaussian row offsets behind the gate flags in the gradient scratch).
-int gs_deterministic();           // api.hip: the knob (or the value a trainer handle pinned for its calls)
-void gs_pin_deterministic(int v); // >= 0: this thread sizes and launches with v until it is reset to -1 (trainer.hip)
+// The two knobs that enter buffer layouts.  A layout is a function of the values it is handed: the public size queries and the
+// stateless operators pass gs_knobs(), a handle passes the values it snapshotted when its workspace was carved.
+struct GsKnobs {
+  int min_units;  // mi355gs_tune_min_units (binning.hip): lengthen the backward's units only while at least this many remain
+  int det;        // mi355gs_tune_deterministic (api.hip)
+};
+GsKnobs gs_knobs();               // api.hip: the process-wide knobs as they stand now
 struct DetScratchLayout {         // behind the 256 bytes of gate flags in the gradient scratch; all uint32
   size_t off, block_sums, total;
   __host__ explicit DetScratchLayout(int P) {
@@ -95,8 +101,7 @@ struct DetScratchLayout {         // behind the 256 bytes of gate flags in the g
     total = o;
   }
 };
-int gs_min_units();               // binning.hip: the mi355gs_tune_min_units knob (or the value a trainer handle pinned for its calls)
-void gs_pin_min_units(int v);     // > 0: this thread sizes and launches with v until it is reset to 0 (trainer.hip)
+int gs_min_units();               // binning.hip: the mi355gs_tune_min_units knob
 constexpr int GS_MIN_UNITS = 40960;  // lengthen units only while at least this many remain (6-7 rounds of the 6144 resident waves:
                                      // measured at C4, 7.3 M instances: 512-instance units 2.34 ms/view, 256: 2.28, 128: 2.21, 64: 2.24)
 
@@ -137,14 +142,14 @@ struct BinningLayout {
   uint32_t max_chunks;  // 64-instance chunks the hit-mask table has room for
   uint32_t max_units;  // table / boundary slots available: an upper bound on the units of any frame with <= R instances
   bool may_loop;       // a frame with this capacity can have units longer than one chunk
-  __host__ BinningLayout(int64_t R, int T) {
+  __host__ BinningLayout(int64_t R, int T, const GsKnobs& knobs) {
     size_t n = R > 0 ? (size_t)R : 1, o = 0;
     keys = o; o += gs_align(n * 8);
     list = o; o += gs_align(n * 4);
     // A frame with c <= R instances runs at level L(c) <= L(R) and has at most c / (64 << L(c)) + T units (one partial unit per
     // tile).  While L(c) is below the top level the rule stopped lengthening, so c / (64 << L(c)) < 2 * min_units; at the top
     // level it is at most R / (64 << top).  Small capacities never exceed ceil(R / 64).
-    const size_t mu = (size_t)gs_min_units(), top = (size_t)GS_SEG << (GS_UNIT_LEVELS - 1);
+    const size_t mu = (size_t)knobs.min_units, top = (size_t)GS_SEG << (GS_UNIT_LEVELS - 1);
     const size_t by_chunks = (n + GS_SEG - 1) / GS_SEG, by_rule = 2 * mu + 1, by_top = (n + top - 1) / top;
     const size_t lim = by_chunks < by_rule ? by_chunks : by_rule;
     may_loop = gs_unit_level_for((long long)n, (long long)mu) > 0;
@@ -158,7 +163,7 @@ struct BinningLayout {
     max_chunks = (uint32_t)(by_chunks + 8 * (size_t)(T > 0 ? T : 1) + 8);
     hitmask = o; o += gs_align((size_t)max_chunks * 4 * sizeof(uint64_t));
     det_rows = det_rowidx = o;
-    if (gs_deterministic()) {   // one row of twelve floats (a GsGrad) and one row index per instance
+    if (knobs.det) {   // one row of twelve floats (a GsGrad) and one row index per instance
       det_rows = o; o += gs_align(n * sizeof(GsGrad));
       det_rowidx = o; o += gs_align(n * 4);
     }
@@ -312,19 +317,18 @@ struct GsProfScope {
   ~GsProfScope();
 };
 
-// Set by the fused train step (trainer.hip) around its calls into the per-operator entry points: the trainer zeroes
-// every counter / accumulator of the iteration in ONE prologue launch and asks the operators to skip their own memsets,
-// and it collects the "gradient tensor has a non-zero" gate flags for PerPointAdam from the kernels that write the
-// gradients (gate[k] > 0  <=>  tensor k of the optimizer's group order has a non-zero gradient) instead of a
-// separate pass over all gradients.
-struct GsPrologue {  // accumulators of one train step, zeroed by the step's first kernel (k_pose_fwd) instead of memsets
+// ---- One frame through the shared kernels (api.hip): what a call means is in its arguments.  The public mi355gs_raster_*
+// entry points build these structs with a default GsFrameCtx; mi355gs_posed_*, the one-call train step (trainer.hip), the pose
+// tracker (tracker.hip) and the camera-path renderer (path.hip) call the gs_frame_* functions with their own.
+
+struct GsPrologue {  // accumulators of one frame, zeroed by the frame's first kernel (the projection) instead of memsets
   float4* grad_records = nullptr; size_t n_vec = 0;      // the 48-byte GsGrad records, as float4
   uint32_t* tile_counters = nullptr; int n_counters = 0;  // per-tile count + cursor
   float* g_poses = nullptr; int n_pose = 0;
   float* pose_scratch = nullptr;                           // 32 floats
   float* adam_scratch = nullptr;                           // 8 gate flags
 };
-// One-call train step: the projection kernels take the RAW parameters (xyz, raw quaternion, log-scale, opacity logit) plus
+// Posed projection: the projection kernels take the RAW parameters (xyz, raw quaternion, log-scale, opacity logit) plus
 // the camera pose and apply InstantSplat's camera-frame transform / activations themselves (pose_math.h), and their
 // backward goes all the way to the raw-parameter gradients and the 16 pose sums — no k_pose_fwd / k_pose_bwd launches
 // and no camera-frame intermediates in HBM.
@@ -333,24 +337,106 @@ struct GsPosed {
   float* acc = nullptr;         // backward: 16 pose sums (see pose_math.h), zeroed by the caller ...
   float* partial = nullptr;     // ... or, if set, one row of 16 per workgroup of the backward projection kernel (no atomics)
 };
-struct GsFusedStepHooks {
-  bool skip_memsets = false;
-  GsPrologue prologue;
-  GsPosed posed;
-  float* gate = nullptr;   // device float[8] or null
-  bool gate_tail = false;  // the flags live right behind the GsGrad records (mi355gs_raster_grad_gate_offset) and are cleared with them
-  uint32_t* adam_live = nullptr;  // device uint32[16] persisting across steps (see k_adam_multi) or null
-  uint32_t adam_seq = 0;          // launch sequence number (never 0) for adam_live
-  // Commit gate of the one-call step (trainer.hip): the frame's true instance count (device word written by the tile scan)
-  // and the capacity of the instance buffers.  An Adam launch that finds count > capacity writes NOTHING — the frame dropped
-  // instances, its gradients are not the iteration's — so the step can be enqueued whole, before the host has seen the count.
-  const uint32_t* commit_count = nullptr;
-  unsigned long long commit_capacity = 0;
-  uint32_t* commit_poison = nullptr;   // device word, sticky: set by a launch that discarded itself; later gated launches then discard themselves too
-  int gate_xyz = -1, gate_rot = -1, gate_scaling = -1, gate_opacity = -1, gate_sh = -1, gate_sh_rest = -1, gate_pose = -1;
-  // Pose tracking (tracker.hip): with `posed` set, the projection backward runs its pose-only instantiation — the chain down to
-  // the 16 pose sums only; no per-Gaussian gradient, screen-space gradient or gate flag is stored, and the output pointers of
-  // mi355gs_raster_backward may be null.
-  bool pose_only = false;
+// "gradient tensor k has a non-zero" flags for PerPointAdam, written by the kernels that write the gradients (gate[k] > 0 <=>
+// tensor k has a non-zero gradient) instead of a separate pass over all gradients: k in the optimizer's group order
+enum { GS_GATE_XYZ = 0, GS_GATE_SH = 1, GS_GATE_SH_REST = 2, GS_GATE_OPACITY = 3, GS_GATE_SCALING = 4, GS_GATE_ROT = 5, GS_GATE_POSE = 6 };
+
+struct GsScene {  // the Gaussians as the operator receives them
+  int P, D, M;
+  const float *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
+  float scale_modifier;
 };
-extern thread_local GsFusedStepHooks g_fused;
+struct GsView {
+  int W, H;
+  const float *view, *proj, *campos;
+  float tanfovx, tanfovy;
+};
+struct GsFrameBufs {  // the frame's scratch buffers (size queries of include/mi355gs.h) and the knobs they were laid out for
+  void *geom, *tiles, *binning;
+  int64_t capacity;   // instances `binning` holds
+  int32_t* radii;
+  void* grad_scratch;
+  GsKnobs knobs;
+};
+struct GsFrameCtx {  // what a fused caller means beyond the operator's arguments; the default is the stateless operator
+  const GsPrologue* prologue = nullptr;  // set: the projection clears exactly this list and the frame issues no memset of its own
+  GsPosed posed;
+  float* gate = nullptr;   // posed backward only: device float[8] of gate flags (GS_GATE_*), or null
+  bool gate_tail = false;  // the flags live right behind the GsGrad records (mi355gs_raster_grad_gate_offset) and are cleared with them
+  bool pose_only = false;  // pose tracking: with `posed` set the projection backward stops at the 16 pose sums — no per-Gaussian
+                           // gradient, screen-space gradient or gate flag is stored, and every GsGradOut pointer may be null
+};
+struct GsGradOut { float *means3D, *means2D, *shs, *shs_rest, *colors, *opacities, *scales, *rotations, *cov3D; };
+static inline size_t gs_grad_gate_offset(int P) { return gs_align((size_t)(P > 0 ? P : 1) * sizeof(GsGrad)); }
+static inline size_t gs_grad_scratch_bytes(int P, int det) { return gs_grad_gate_offset(P) + 256 + (det ? DetScratchLayout(P).total : 0); }
+static inline size_t gs_binning_bytes(int64_t n, int W, int H, const GsKnobs& k, bool train) {
+  const BinningLayout bl(n, TilesLayout(W, H).T, k);
+  return train ? bl.total : bl.unit_tile;   // render-only: keys + list, everything in front of the backward's tables
+}
+// the frame's true instance count: tile_start[T], written by the tile scan
+static inline const uint32_t* gs_frame_count(const void* tiles, int W, int H) {
+  const TilesLayout tl(W, H);
+  return (const uint32_t*)((const char*)tiles + tl.start) + tl.T;
+}
+// projection + tile count + tile scan; stage 2 (train: leaves the backward's tables; else render-only); backward
+int gs_frame_project(hipStream_t stream, const GsScene& sc, const GsView& vw, const GsFrameBufs& fb, const GsFrameCtx& cx,
+                     int32_t* num_rendered, uint8_t* visible, int debug);
+int gs_frame_render(hipStream_t stream, int P, const GsView& vw, const GsFrameBufs& fb, const float* bg, float* out_color, bool train,
+                    int debug);
+int gs_frame_backward(hipStream_t stream, const GsScene& sc, const GsView& vw, const GsFrameBufs& fb, const GsFrameCtx& cx,
+                      const float* bg, const float* out_color, const float* dL_dpix, const GsGradOut& out, bool grad_scratch_is_clear,
+                      int debug);
+
+// Multi-tensor PerPointAdam (adam.hip).  `fused` (the one-call train step's launches) or null:
+struct GsAdamFused {
+  uint32_t* live; uint32_t seq;     // device uint32[16] persisting across steps (see k_adam_multi) and the launch's sequence number (never 0)
+  // Commit gate: the frame's true instance count (gs_frame_count) and the capacity of the instance buffers, or a null count.  A
+  // launch that finds count > capacity writes NOTHING — the frame dropped instances, its gradients are not the iteration's — so
+  // the step can be enqueued whole, before the host has seen the count.
+  const uint32_t* commit_count; unsigned long long commit_capacity;
+  uint32_t* commit_poison;          // device word, sticky: set by a launch that discarded itself; later gated launches then discard themselves too
+};
+// With `fused`, scratch[t] is tensor t's gate flag, written by the kernels that produced the gradients.
+int gs_adam_multi(hipStream_t stream, int ntensors, const int64_t* numel, const int32_t* row, float* const* params,
+                  const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const float* const* per_point_lr,
+                  const float* lr, float beta1, float beta2, float eps, const int32_t* step, float* scratch, const float* gate,
+                  const int32_t* gate_index, uint32_t* live, uint32_t seq, const GsAdamFused* fused);
+
+// ---- What the handles over a FROZEN scene share (pose tracker, camera-path renderer): the scene, the buffers of one posed frame
+// carved from the caller's workspace, and that frame's arguments.
+struct GsFrozenScene {
+  int P, M, W, H;
+  int64_t capacity;
+  const float *xyz, *f_dc, *f_rest, *opacity, *scaling, *rotation;
+  char *geom, *tiles, *binning;
+  float *image, *consts;   // consts: identity view [16], campos [3] (gs_launch_view_consts)
+  int32_t *radii, *num_rendered;   // num_rendered: where the tile scan leaves its copy of the count; the handles read count()
+
+  // create-time checks and the scene's fields; false: refuse the handle
+  bool init(int P_, int M_, int W_, int H_, int64_t capacity_, const float* xyz_, const float* f_dc_, const float* f_rest_,
+            const float* opacity_, const float* scaling_, const float* rotation_, const void* workspace) {
+    if (P_ <= 0 || M_ < 1 || M_ > 16 || W_ <= 0 || H_ <= 0 || W_ > 65535 * GS_TILE || H_ > 65535 * GS_TILE || capacity_ <= 0 || !workspace)
+      return false;
+    if (!xyz_ || !f_dc_ || (M_ > 1 && !f_rest_) || !opacity_ || !scaling_ || !rotation_) return false;
+    P = P_; M = M_; W = W_; H = H_; capacity = capacity_;
+    xyz = xyz_; f_dc = f_dc_; f_rest = M_ > 1 ? f_rest_ : nullptr; opacity = opacity_; scaling = scaling_; rotation = rotation_;
+    return true;
+  }
+  // train: `binning` holds the backward's tables too, laid out for `knobs`; else keys + lists only (the same for any knobs)
+  void carve(GsCarver& c, const GsKnobs& knobs, bool train) {
+    geom = c.take<char>(GeomLayout(P).total);
+    tiles = c.take<char>(TilesLayout(W, H).total);
+    binning = c.take<char>(gs_binning_bytes(capacity, W, H, knobs, train));
+    image = c.take<float>(3 * (size_t)W * H);
+    consts = c.take<float>(32);
+    radii = c.take<int32_t>((size_t)P);
+    num_rendered = c.take<int32_t>(1);
+  }
+  bool degree_ok(int D) const { return D >= 0 && D <= 3 && (D + 1) * (D + 1) <= M; }
+  GsScene scene(int D) const {   // degree 0 reads only the DC coefficient; higher degrees read f_dc + f_rest in place
+    return {P, D, D == 0 ? 1 : M, xyz, f_dc, D == 0 ? nullptr : f_rest, nullptr, opacity, scaling, rotation, nullptr, 1.0f};
+  }
+  GsView view(const float* proj, float tanfovx, float tanfovy) const { return {W, H, consts, proj, consts + 16, tanfovx, tanfovy}; }
+  GsFrameBufs bufs(const GsKnobs& knobs, void* grad_scratch) const { return {geom, tiles, binning, capacity, radii, grad_scratch, knobs}; }
+  const uint32_t* count() const { return gs_frame_count(tiles, W, H); }
+};

@@ -6,7 +6,8 @@
 // 7 kernel dispatches per frame (projection, tile count, tile scan, scatter, tile sort, composite, 8-bit conversion), no host
 // synchronisation, no memset and no allocation: every buffer lives in one caller-provided workspace, the frames go straight to
 // the caller's [N,H,W,3] byte array — device memory, or pinned host memory the device can write.  The projection, binning and
-// composite kernels are the ones a no-grad render() runs, reached through the same thread-local hook (GsFusedStepHooks::posed).
+// composite kernels are the ones a no-grad render() runs, called through the same frame functions (common.h, gs_frame_*) with
+// the frame's pose as their only context: the projection clears the per-tile counters on its way, as in a stateless render.
 #include <stdlib.h>
 #include <string.h>
 #include "common.h"
@@ -70,42 +71,13 @@ int launch_rgb8(hipStream_t stream, int W, int H, const float* img, uint8_t* out
   return MI355GS_OK;
 }
 
-struct Path {
-  int P, M, W, H;
-  int64_t capacity;
-  const float *xyz, *f_dc, *f_rest, *opacity, *scaling, *rotation;
-  char *geom, *tiles, *binning;
-  float *image, *consts;   // consts: identity view [16], campos [3]
-  int32_t *radii, *num_rendered;
-};
+typedef GsFrozenScene Path;   // nothing of its own: render-only buffers, which no knob enters
 
 size_t carve(Path& t, void* workspace) {
   GsCarver c{(char*)workspace};
-  const size_t P = (size_t)(t.P > 0 ? t.P : 1), npix = (size_t)t.W * t.H;
-  t.geom = c.take<char>(mi355gs_raster_geom_bytes(t.P));
-  t.tiles = c.take<char>(mi355gs_raster_tiles_bytes(t.W, t.H));
-  t.binning = c.take<char>(mi355gs_raster_binning_bytes_render_only(t.capacity, t.W, t.H));
-  t.image = c.take<float>(3 * npix);
-  t.consts = c.take<float>(32);
-  t.radii = c.take<int32_t>(P);
-  t.num_rendered = c.take<int32_t>(1);   // where the tile scan leaves its copy of the count; the frames' come from tile_start[T]
+  t.carve(c, gs_knobs(), false);
   return c.off;
 }
-
-// Written at the head of EVERY call, on that call's stream (a 2 us launch against n frames of ~120): a handle may then be used
-// on any stream, one call at a time, without an ordering between the call that first wrote them and a later one elsewhere.
-int write_consts(Path* t, hipStream_t stream) {
-  const int debug = 0;
-  GS_KRANGE("view_consts");
-  gs_launch_view_consts(stream, t->consts);
-  GS_CHECK_LAUNCH("view_consts");
-  return MI355GS_OK;
-}
-
-// the hook of one call, released however it returns
-struct HookScope {
-  ~HookScope() { g_fused = GsFusedStepHooks(); }
-};
 
 }  // namespace
 
@@ -127,13 +99,10 @@ size_t mi355gs_path_workspace_bytes(int P, int W, int H, int64_t capacity) {
 
 void* mi355gs_path_create(int P, int M, int W, int H, int64_t capacity, const float* xyz, const float* f_dc, const float* f_rest,
                           const float* opacity, const float* scaling, const float* rotation, void* workspace) {
-  if (P <= 0 || M < 1 || M > 16 || !rgb8_size_ok(W, H) || W > 65535 * GS_TILE || H > 65535 * GS_TILE || capacity <= 0 || !workspace)
-    return nullptr;
-  if (!xyz || !f_dc || (M > 1 && !f_rest) || !opacity || !scaling || !rotation) return nullptr;
+  if (!rgb8_size_ok(W, H)) return nullptr;
   Path* t = (Path*)calloc(1, sizeof(Path));
   if (!t) return nullptr;
-  t->P = P; t->M = M; t->W = W; t->H = H; t->capacity = capacity;
-  t->xyz = xyz; t->f_dc = f_dc; t->f_rest = M > 1 ? f_rest : nullptr; t->opacity = opacity; t->scaling = scaling; t->rotation = rotation;
+  if (!t->init(P, M, W, H, capacity, xyz, f_dc, f_rest, opacity, scaling, rotation, workspace)) { free(t); return nullptr; }
   carve(*t, workspace);
   return t;
 }
@@ -145,29 +114,23 @@ int mi355gs_path_render(void* handle, void* stream_, int sh_degree, const float*
   GS_RANGE();
   Path* t = (Path*)handle;
   hipStream_t stream = (hipStream_t)stream_;
-  if (!t || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > t->M || !projmatrix || !bg || !poses || !frames ||
-      !counts)
-    return MI355GS_EINVAL;
+  if (!t || !t->degree_ok(sh_degree) || !projmatrix || !bg || !poses || !frames || !counts) return MI355GS_EINVAL;
   if (first < 0 || n < 0 || n > 0x7fffffff - first) return MI355GS_EINVAL;
   if (n == 0) return MI355GS_OK;
   int rc;
-  if ((rc = write_consts(t, stream))) return rc;
-  const int P = t->P, W = t->W, H = t->H, D = sh_degree, M = D == 0 ? 1 : t->M;
-  const float* rest = D == 0 ? nullptr : t->f_rest;
-  const TilesLayout tl(W, H);
-  const uint32_t* count = (const uint32_t*)(t->tiles + tl.start) + tl.T;   // tile_start[T]: the frame's instance count
-  const size_t frame_bytes = (size_t)W * H * 3;
-  HookScope scope;
+  // The constants are written at the head of EVERY call, on that call's stream (a 2 us launch against n frames of ~120): a handle may
+  // then be used on any stream, one call at a time, without an ordering between the call that first wrote them and a later one elsewhere.
+  if ((rc = gs_write_view_consts(stream, t->consts, "view_consts"))) return rc;
+  const GsScene scene = t->scene(sh_degree);
+  const GsView view = t->view(projmatrix, tanfovx, tanfovy);
+  const GsFrameBufs bufs = t->bufs(gs_knobs(), nullptr);
+  const size_t frame_bytes = (size_t)t->W * t->H * 3;
   for (int i = first; i < first + n; ++i) {
-    // the frame's per-tile counters are cleared by its first kernel, the projection
-    g_fused = GsFusedStepHooks();
-    g_fused.posed.pose = poses + 7 * (size_t)i;
-    if ((rc = mi355gs_raster_forward_preprocess(stream, P, D, M, W, H, t->xyz, t->f_dc, rest, nullptr, t->opacity, t->scaling, 1.0f,
-                                                t->rotation, nullptr, t->consts, projmatrix, t->consts + 16, tanfovx, tanfovy, 0,
-                                                t->radii, t->geom, t->tiles, t->num_rendered, nullptr, nullptr, 0)))
-      return rc;
-    if ((rc = mi355gs_raster_forward_render_only(stream, P, W, H, t->capacity, bg, t->geom, t->tiles, t->binning, t->image, 0))) return rc;
-    if ((rc = launch_rgb8(stream, W, H, t->image, frames + frame_bytes * (size_t)i, count, counts + i))) return rc;
+    GsFrameCtx cx;
+    cx.posed.pose = poses + 7 * (size_t)i;
+    if ((rc = gs_frame_project(stream, scene, view, bufs, cx, t->num_rendered, nullptr, 0))) return rc;
+    if ((rc = gs_frame_render(stream, t->P, view, bufs, bg, t->image, false, 0))) return rc;
+    if ((rc = launch_rgb8(stream, t->W, t->H, t->image, frames + frame_bytes * (size_t)i, t->count(), counts + i))) return rc;
   }
   return MI355GS_OK;
 }

@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void k_pose_fwd(int P, const float* __restrict
                                                    GsPrologue pro) {
   const PoseMat m = load_pose(pose);
   const int stride = gridDim.x * blockDim.x;
-  if (pro.grad_records) {  // first kernel of a fused train step: clear the step's accumulators on the way
+  if (pro.grad_records) {  // clear a step's accumulators on the way (no caller hands a list over since the posed projection does it)
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
     for (size_t i = gid; i < pro.n_vec; i += (size_t)stride) pro.grad_records[i] = z;
@@ -185,7 +185,7 @@ int mi355gs_pose_forward(void* stream_, int P, const float* xyz, const float* ro
   const int blocks = min((P + 255) / 256, 4096);
   GS_KRANGE("pose_fwd");
   hipLaunchKernelGGL(k_pose_fwd, dim3(blocks), dim3(256), 0, stream, P, xyz, rot, scaling, opacity_logit, pose, means_cam, rot_cam,
-                     scales, opac, g_fused.prologue);
+                     scales, opac, GsPrologue());   // (no accumulators to clear on the way: the stateless operator)
   GS_CHECK_LAUNCH("pose_fwd");
   return MI355GS_OK;
 }
@@ -198,8 +198,7 @@ int mi355gs_pose_backward(void* stream_, int P, const float* xyz, const float* r
   hipStream_t stream = (hipStream_t)stream_;
   const int debug = 0;
   if (P < 0 || !pose || !d_pose || !scratch16) return MI355GS_EINVAL;
-  if (!g_fused.skip_memsets && hipMemsetAsync(scratch16, 0, 32 * sizeof(float), stream) != hipSuccess) return MI355GS_ELAUNCH;
-  float* pose_gate = (g_fused.gate && g_fused.gate_pose >= 0) ? g_fused.gate + g_fused.gate_pose : nullptr;
+  if (hipMemsetAsync(scratch16, 0, 32 * sizeof(float), stream) != hipSuccess) return MI355GS_ELAUNCH;
   if (P > 0) {
     if (!xyz || !rot || !scales || !opac || !g_means || !g_rot || !g_scales || !g_opac || !d_xyz || !d_rot || !d_scaling ||
         !d_opacity_logit)
@@ -207,13 +206,12 @@ int mi355gs_pose_backward(void* stream_, int P, const float* xyz, const float* r
     const int blocks = min((P + 255) / 256, 1024);
     GS_KRANGE("pose_bwd");
     hipLaunchKernelGGL(k_pose_bwd, dim3(blocks), dim3(256), 0, stream, P, xyz, rot, scales, opac, pose, g_means, g_rot, g_scales,
-                       g_opac, d_xyz, d_rot, d_scaling, d_opacity_logit, scratch16, g_fused.gate, g_fused.gate_xyz, g_fused.gate_rot,
-                       g_fused.gate_scaling, g_fused.gate_opacity);
+                       g_opac, d_xyz, d_rot, d_scaling, d_opacity_logit, scratch16, (float*)nullptr, -1, -1, -1, -1);   // (no gate flags)
     GS_CHECK_LAUNCH("pose_bwd");
   }
   // (folding this into k_pose_bwd's last workgroup was measured: the ticket round trips cost more than the launch)
   GS_KRANGE("pose_finish");
-  hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(64), 0, stream, pose, (const float*)scratch16, d_pose, pose_gate);
+  hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(64), 0, stream, pose, (const float*)scratch16, d_pose, (float*)nullptr);
   GS_CHECK_LAUNCH("pose_finish");
   return MI355GS_OK;
 }

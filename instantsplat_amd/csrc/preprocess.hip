@@ -558,10 +558,10 @@ int gs_launch_preprocess_fwd(hipStream_t stream, int P, int D, int M, const floa
                              const float* colors_precomp, const float* opacities, const float* scales,
                              const float* rotations, const float* cov3D_precomp, const CamParams& cp, int32_t* radii,
                              GsRec* recs, float* cov3Ds, uint2* rects, uint8_t* clamped, float* depths, uint8_t* visible,
-                             const GsPrologue& pro) {
+                             const GsPosed& posed_args, const GsPrologue& pro) {
   if (P <= 0) return 0;
-  const bool posed = g_fused.posed.pose != nullptr;
-  const GsPosed pa = posed ? g_fused.posed : GsPosed();
+  const bool posed = posed_args.pose != nullptr;
+  const GsPosed pa = posed ? posed_args : GsPosed();
 #define GS_FWD(POSED, DEG)                                                                                                              \
   hipLaunchKernelGGL((k_preprocess_fwd<POSED, DEG>), dim3((P + 255) / 256), dim3(256), 0, stream, P, M, means3D, shs, shs_rest,         \
                      colors_precomp, opacities, scales, rotations, cov3D_precomp, cp, radii, recs, cov3Ds, rects, clamped, depths, visible, pa, pro)
@@ -576,21 +576,24 @@ int gs_launch_preprocess_bwd(hipStream_t stream, int P, int D, int M, const floa
                              const float* scales, const float* rotations, int use_shs, int use_cov_precomp,
                              const CamParams& cp, const int32_t* radii, const GsRec* recs, const float* cov3Ds, const uint8_t* clamped,
                              const GsGrad* grads, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dshs_rest,
-                             float* dL_dcolors, float* dL_dopac, float* dL_dscales, float* dL_drots, float* dL_dcov3D, float* sh_gate,
-                             float* sh_rest_gate) {
+                             float* dL_dcolors, float* dL_dopac, float* dL_dscales, float* dL_drots, float* dL_dcov3D,
+                             const GsPosed& posed_args, float* gate_flags, bool pose_only) {
   if (P <= 0) return 0;
-  const bool posed = g_fused.posed.pose != nullptr;
-  const GsPosed pa = posed ? g_fused.posed : GsPosed();
-  float* gate = posed ? g_fused.gate : nullptr;
-  const int gi[4] = {posed ? g_fused.gate_xyz : -1, posed ? g_fused.gate_rot : -1, posed ? g_fused.gate_scaling : -1,
-                     posed ? g_fused.gate_opacity : -1};
+  const bool posed = posed_args.pose != nullptr;
+  const GsPosed pa = posed ? posed_args : GsPosed();
+  // the gate flags (GS_GATE_*): the SH ones are written by either form of the kernel, the four others by the posed form only
+  float* sh_gate = gate_flags ? gate_flags + GS_GATE_SH : nullptr;
+  float* sh_rest_gate = gate_flags ? gate_flags + GS_GATE_SH_REST : nullptr;
+  float* gate = posed ? gate_flags : nullptr;
+  const bool gi_on = posed && gate_flags;
+  const int gi[4] = {gi_on ? GS_GATE_XYZ : -1, gi_on ? GS_GATE_ROT : -1, gi_on ? GS_GATE_SCALING : -1, gi_on ? GS_GATE_OPACITY : -1};
 #define GS_BWD(POSED, DEG, ...)                                                                                                         \
   hipLaunchKernelGGL((k_preprocess_bwd<POSED, DEG, ##__VA_ARGS__>), dim3((P + 255) / 256), dim3(256), 0, stream, P, M, means3D, shs, shs_rest, scales, \
                      rotations, use_shs, use_cov_precomp, cp, radii, recs, cov3Ds, clamped, grads, dL_dmeans3D, dL_dmeans2D, dL_dshs,  \
                      dL_dshs_rest, dL_dcolors, dL_dopac, dL_dscales, dL_drots, dL_dcov3D, sh_gate, sh_rest_gate, pa, gate, gi[0],     \
                      gi[1], gi[2], gi[3])
   const int deg = use_shs ? D : 0;
-  if (posed && g_fused.pose_only) {
+  if (posed && pose_only) {
     if (deg == 0) GS_BWD(true, 0, true); else if (deg == 1) GS_BWD(true, 1, true); else if (deg == 2) GS_BWD(true, 2, true); else GS_BWD(true, 3, true);
   } else if (posed) { if (deg == 0) GS_BWD(true, 0); else if (deg == 1) GS_BWD(true, 1); else if (deg == 2) GS_BWD(true, 2); else GS_BWD(true, 3); }
   else { if (deg == 0) GS_BWD(false, 0); else if (deg == 1) GS_BWD(false, 1); else if (deg == 2) GS_BWD(false, 2); else GS_BWD(false, 3); }

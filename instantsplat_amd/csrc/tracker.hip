@@ -7,8 +7,9 @@
 // 10 kernel dispatches per iteration (projection, tile count, tile scan, scatter, tile sort, composite, masked L1, composite
 // backward, projection backward, finish; 12 in deterministic mode with det_prepare / det_gather around the composite backward), no host
 // synchronisation and no allocation: every buffer lives in one caller-provided workspace, the optimizer state in a caller-owned
-// device block.  The projection, binning and composite kernels are the ones render() and the one-call train step run, reached
-// through the same thread-local hooks (GsFusedStepHooks); the projection backward runs its pose-only instantiation, which
+// device block.  The projection, binning and composite kernels are the ones render() and the one-call train step run, called
+// through the same frame functions (common.h, gs_frame_*) with this loop's context: the pose and the rows for its sums, the
+// frame's accumulators cleared by the projection, and the projection backward in its pose-only instantiation, which
 // stores none of the ~250 B per Gaussian of raw-parameter gradients and gate flags that frozen Gaussians never read.
 #include <stdlib.h>
 #include <string.h>
@@ -22,30 +23,20 @@ constexpr int L1_BLOCK = 256 * L1_PER_THREAD;
 
 int l1_nblocks(int W, int H) { return (int)((3LL * W * H + L1_BLOCK - 1) / L1_BLOCK); }
 
-struct Tracker {
-  int P, M, W, H;
-  int64_t capacity;
-  const float *xyz, *f_dc, *f_rest, *opacity, *scaling, *rotation;
-  char *geom, *tiles, *binning, *grad_scratch;
-  float *image, *dL_dimg, *loss_partial, *pose_partial, *consts;  // consts: identity view [16], campos [3]
-  int32_t *radii, *num_rendered;
+struct Tracker : GsFrozenScene {
+  char* grad_scratch;
+  float *dL_dimg, *loss_partial, *pose_partial;
   bool consts_ready;
-  int det, min_units;   // the knobs as they stood at create: the buffers were laid out for them
+  GsKnobs knobs;   // as they stood at create: the buffers were laid out for them
 };
 
 size_t carve(Tracker& t, void* workspace) {
   GsCarver c{(char*)workspace};
-  const size_t P = (size_t)(t.P > 0 ? t.P : 1), npix = (size_t)t.W * t.H;
-  t.geom = c.take<char>(mi355gs_raster_geom_bytes(t.P));
-  t.tiles = c.take<char>(mi355gs_raster_tiles_bytes(t.W, t.H));
-  t.binning = c.take<char>(mi355gs_raster_binning_bytes(t.capacity, t.W, t.H));
-  t.grad_scratch = c.take<char>(mi355gs_raster_grad_scratch_bytes(t.P));
-  t.image = c.take<float>(3 * npix); t.dL_dimg = c.take<float>(3 * npix);
+  t.GsFrozenScene::carve(c, t.knobs, true);
+  t.grad_scratch = c.take<char>(gs_grad_scratch_bytes(t.P, t.knobs.det));
+  t.dL_dimg = c.take<float>(3 * (size_t)t.W * t.H);
   t.loss_partial = c.take<float>(2 * (size_t)l1_nblocks(t.W, t.H));
-  t.pose_partial = c.take<float>(16 * ((P + 255) / 256));
-  t.consts = c.take<float>(32);
-  t.radii = c.take<int32_t>(P);
-  t.num_rendered = c.take<int32_t>(1);
+  t.pose_partial = c.take<float>(16 * (((size_t)t.P + 255) / 256));
   return c.off;
 }
 
@@ -200,23 +191,11 @@ __global__ __launch_bounds__(1024) void k_tracker_finish(const float* __restrict
   }
 }
 
-// the pins and hooks of one call, released however it returns
-struct HookScope {
-  HookScope(const Tracker& t) {
-    gs_pin_min_units(t.min_units);
-    gs_pin_deterministic(t.det);
-  }
-  ~HookScope() { g_fused = GsFusedStepHooks(); gs_pin_min_units(0); gs_pin_deterministic(-1); }
-};
-
-int ensure_consts(Tracker* t, hipStream_t stream) {
-  const int debug = 0;
+int ensure_consts(Tracker* t, hipStream_t stream) {   // written once, on the stream of the handle's first call
   if (t->consts_ready) return MI355GS_OK;
-  GS_KRANGE("tracker_consts");
-  gs_launch_view_consts(stream, t->consts);
-  GS_CHECK_LAUNCH("tracker_consts");
-  t->consts_ready = true;
-  return MI355GS_OK;
+  const int rc = gs_write_view_consts(stream, t->consts, "tracker_consts");
+  t->consts_ready = rc == MI355GS_OK;
+  return rc;
 }
 
 }  // namespace
@@ -227,21 +206,16 @@ size_t mi355gs_tracker_workspace_bytes(int P, int W, int H, int64_t capacity) {
   if (P <= 0 || W <= 0 || H <= 0 || capacity <= 0) return 0;
   Tracker t;
   memset(&t, 0, sizeof(t));
-  t.P = P; t.W = W; t.H = H; t.capacity = capacity;
+  t.P = P; t.W = W; t.H = H; t.capacity = capacity; t.knobs = gs_knobs();
   return carve(t, nullptr);
 }
 
 void* mi355gs_tracker_create(int P, int M, int W, int H, int64_t capacity, const float* xyz, const float* f_dc, const float* f_rest,
                              const float* opacity, const float* scaling, const float* rotation, void* workspace) {
-  if (P <= 0 || M < 1 || M > 16 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE || capacity <= 0 || !workspace)
-    return nullptr;
-  if (!xyz || !f_dc || (M > 1 && !f_rest) || !opacity || !scaling || !rotation) return nullptr;
   Tracker* t = (Tracker*)calloc(1, sizeof(Tracker));
   if (!t) return nullptr;
-  t->P = P; t->M = M; t->W = W; t->H = H; t->capacity = capacity;
-  t->xyz = xyz; t->f_dc = f_dc; t->f_rest = M > 1 ? f_rest : nullptr; t->opacity = opacity; t->scaling = scaling; t->rotation = rotation;
-  t->min_units = gs_min_units();
-  t->det = gs_deterministic();
+  if (!t->init(P, M, W, H, capacity, xyz, f_dc, f_rest, opacity, scaling, rotation, workspace)) { free(t); return nullptr; }
+  t->knobs = gs_knobs();
   carve(*t, workspace);
   return t;
 }
@@ -253,16 +227,13 @@ int mi355gs_tracker_count(void* handle, void* stream_, int sh_degree, const floa
   GS_RANGE();
   Tracker* t = (Tracker*)handle;
   hipStream_t stream = (hipStream_t)stream_;
-  if (!t || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > t->M || !projmatrix || !pose || !count_out)
-    return MI355GS_EINVAL;
+  if (!t || !t->degree_ok(sh_degree) || !projmatrix || !pose || !count_out) return MI355GS_EINVAL;
   int rc;
   if ((rc = ensure_consts(t, stream))) return rc;
-  HookScope scope(*t);
-  g_fused.posed.pose = pose;
-  const int D = sh_degree;
-  return mi355gs_raster_forward_preprocess(stream, t->P, D, D == 0 ? 1 : t->M, t->W, t->H, t->xyz, t->f_dc, D == 0 ? nullptr : t->f_rest,
-                                           nullptr, t->opacity, t->scaling, 1.0f, t->rotation, nullptr, t->consts, projmatrix,
-                                           t->consts + 16, tanfovx, tanfovy, 0, t->radii, t->geom, t->tiles, count_out, nullptr, nullptr, 0);
+  GsFrameCtx cx;
+  cx.posed.pose = pose;
+  return gs_frame_project(stream, t->scene(sh_degree), t->view(projmatrix, tanfovx, tanfovy), t->bufs(t->knobs, nullptr), cx, count_out,
+                          nullptr, 0);
 }
 
 int mi355gs_tracker_run(void* handle, void* stream_, int sh_degree, const float* gt_image, const float* projmatrix, float tanfovx,
@@ -272,47 +243,37 @@ int mi355gs_tracker_run(void* handle, void* stream_, int sh_degree, const float*
   Tracker* t = (Tracker*)handle;
   hipStream_t stream = (hipStream_t)stream_;
   const int debug = 0;
-  if (!t || sh_degree < 0 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > t->M || !gt_image || !projmatrix || !bg || !sched ||
-      !state)
-    return MI355GS_EINVAL;
+  if (!t || !t->degree_ok(sh_degree) || !gt_image || !projmatrix || !bg || !sched || !state) return MI355GS_EINVAL;
   if (num_iter <= 0 || first_iter < 0 || n_iters < 0 || first_iter > num_iter || n_iters > num_iter - first_iter) return MI355GS_EINVAL;
   if (n_iters == 0) return MI355GS_OK;
   int rc;
   if ((rc = ensure_consts(t, stream))) return rc;
-  const int P = t->P, W = t->W, H = t->H, D = sh_degree, M = D == 0 ? 1 : t->M;
-  const float* rest = D == 0 ? nullptr : t->f_rest;
-  const float* view_m = t->consts;
-  const float* campos = t->consts + 16;
+  const int P = t->P, W = t->W, H = t->H;
   const TilesLayout tl(W, H);
-  const uint32_t* count = (const uint32_t*)(t->tiles + tl.start) + tl.T;   // tile_start[T]: the frame's instance count
   const int n_pix = 3 * W * H, l1_blocks = l1_nblocks(W, H), rows = (P + 255) / 256;
-  HookScope scope(*t);
+  const GsScene scene = t->scene(sh_degree);
+  const GsView view = t->view(projmatrix, tanfovx, tanfovy);
+  const GsFrameBufs bufs = t->bufs(t->knobs, t->grad_scratch);
+  // the frame's accumulators (moment records, per-tile counters) are cleared by its first kernel, the projection
+  GsPrologue pro;
+  pro.grad_records = (float4*)t->grad_scratch; pro.n_vec = (size_t)P * 3;
+  pro.tile_counters = (uint32_t*)(t->tiles + tl.count); pro.n_counters = (int)((tl.start - tl.count) / 4);
+  GsFrameCtx cx;
+  cx.prologue = &pro;
+  cx.posed.pose = state + MI355GS_TRACKER_POSE;
+  cx.posed.acc = t->pose_partial;     // unused with `partial` set; kept valid
+  cx.posed.partial = t->pose_partial; // one row of 16 pose sums per projection workgroup
+  cx.pose_only = true;
   for (int it = first_iter; it < first_iter + n_iters; ++it) {
-    // the frame's accumulators (moment records, per-tile counters) are cleared by its first kernel, the projection
-    g_fused = GsFusedStepHooks();
-    g_fused.skip_memsets = true;
-    g_fused.prologue.grad_records = (float4*)t->grad_scratch; g_fused.prologue.n_vec = (size_t)P * 3;
-    g_fused.prologue.tile_counters = (uint32_t*)(t->tiles + tl.count); g_fused.prologue.n_counters = (int)((tl.start - tl.count) / 4);
-    g_fused.posed.pose = state + MI355GS_TRACKER_POSE;
-    g_fused.posed.acc = t->pose_partial;     // unused with `partial` set; kept valid
-    g_fused.posed.partial = t->pose_partial; // one row of 16 pose sums per projection workgroup
-    g_fused.pose_only = true;
-    if ((rc = mi355gs_raster_forward_preprocess(stream, P, D, M, W, H, t->xyz, t->f_dc, rest, nullptr, t->opacity, t->scaling, 1.0f,
-                                                t->rotation, nullptr, view_m, projmatrix, campos, tanfovx, tanfovy, 0, t->radii,
-                                                t->geom, t->tiles, t->num_rendered, nullptr, nullptr, 0)))
-      return rc;
-    if ((rc = mi355gs_raster_forward_render(stream, P, W, H, t->capacity, bg, t->geom, t->tiles, t->binning, t->image, 0))) return rc;
+    if ((rc = gs_frame_project(stream, scene, view, bufs, cx, t->num_rendered, nullptr, 0))) return rc;
+    if ((rc = gs_frame_render(stream, P, view, bufs, bg, t->image, true, 0))) return rc;
     GS_KRANGE("masked_l1");
     hipLaunchKernelGGL(k_masked_l1, dim3(l1_blocks), dim3(256), 0, stream, n_pix, t->image, gt_image, t->dL_dimg, t->loss_partial);
     GS_CHECK_LAUNCH("masked_l1");
-    if ((rc = mi355gs_raster_backward(stream, P, D, M, W, H, bg, t->xyz, t->f_dc, rest, nullptr, t->opacity, t->scaling, 1.0f, t->rotation,
-                                      nullptr, view_m, projmatrix, campos, tanfovx, tanfovy, t->geom, t->tiles, t->binning, t->capacity,
-                                      t->radii, t->image, t->dL_dimg, t->grad_scratch, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, nullptr, nullptr, 0, 0)))
-      return rc;
+    if ((rc = gs_frame_backward(stream, scene, view, bufs, cx, bg, t->image, t->dL_dimg, GsGradOut(), false, 0))) return rc;
     GS_KRANGE("tracker_finish");
     hipLaunchKernelGGL(k_tracker_finish, dim3(1), dim3(1024), 0, stream, (const float*)t->pose_partial, rows,
-                       (const float*)t->loss_partial, l1_blocks, count, (const uint32_t*)(t->tiles + tl.qmax), 4 * tl.T,
+                       (const float*)t->loss_partial, l1_blocks, t->count(), (const uint32_t*)(t->tiles + tl.qmax), 4 * tl.T,
                        (unsigned long long)t->capacity, (const float4*)sched, it, state,
                        pose_trace, loss_trace, grad_trace);
     GS_CHECK_LAUNCH("tracker_finish");

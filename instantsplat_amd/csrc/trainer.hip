@@ -9,8 +9,9 @@
 //
 // 11 kernel launches (projection, tile count, tile scan, scatter, tile sort, composite, fused loss, composite backward,
 // projection backward, pose finish + loss value, PerPointAdam), no host synchronisation, no temporary allocation: every buffer lives in one caller-provided
-// workspace that the trainer carves up once.  The same kernels (and launch helpers) as the op-by-op path are used,
-// so results are identical up to the order of float atomics.  The instance buffers have a fixed capacity; the
+// workspace that the trainer carves up once.  The same kernels as the op-by-op path are used, through the same frame functions
+// (common.h, gs_frame_*) with the step's context passed as arguments: the accumulators its projection clears, the pose, the
+// gate flags its backward writes for PerPointAdam.  Results are identical up to the order of float atomics.  The instance buffers have a fixed capacity; the
 // true count is written to *num_rendered every step so the caller can verify it asynchronously.
 #include <stdlib.h>
 #include <string.h>
@@ -41,19 +42,17 @@ struct Trainer {
   uint32_t* adam_live;  // see MultiAdamArgs::live
   uint32_t adam_seq;
   bool consts_ready;
-  int det;         // the deterministic-backward knob at the same moment (it enters the layouts too)
-  int min_units;   // the unit-length knob as it stood when the workspace was carved: every later call of the handle sizes and
-                   // launches with THIS value, whatever mi355gs_tune_min_units has been set to since (the buffers were laid
-                   // out for it)
+  GsKnobs knobs;   // as they stood when the workspace was carved: every later call of the handle sizes and launches with THESE
+                   // values, whatever mi355gs_tune_* has been set to since (the buffers were laid out for them)
 };
 
 size_t carve(Trainer& t, void* workspace) {
   GsCarver c{(char*)workspace};
   const size_t P = (size_t)(t.P > 0 ? t.P : 1), npix = (size_t)t.W * t.H;
-  t.geom = c.take<char>(mi355gs_raster_geom_bytes(t.P));
-  t.tiles = c.take<char>(mi355gs_raster_tiles_bytes(t.W, t.H));
-  t.binning = c.take<char>(mi355gs_raster_binning_bytes(t.capacity, t.W, t.H));
-  t.grad_scratch = c.take<char>(mi355gs_raster_grad_scratch_bytes(t.P));
+  t.geom = c.take<char>(GeomLayout(t.P).total);
+  t.tiles = c.take<char>(TilesLayout(t.W, t.H).total);
+  t.binning = c.take<char>(gs_binning_bytes(t.capacity, t.W, t.H, t.knobs, true));
+  t.grad_scratch = c.take<char>(gs_grad_scratch_bytes(t.P, t.knobs.det));
   t.ssim_scratch = c.take<char>(mi355gs_ssim_scratch_bytes(1, 3, t.H, t.W));
   t.image = c.take<float>(3 * npix); t.dL_dimg = c.take<float>(3 * npix);
   t.radii = c.take<int32_t>(P);
@@ -66,7 +65,8 @@ size_t carve(Trainer& t, void* workspace) {
 }
 
 // commit_gate: the launch is part of the step that produced the gradients and has not been cleared by the host — it must
-// turn itself into a no-op when that frame's instance count exceeded the buffers (see GsFusedStepHooks::commit_count)
+// turn itself into a no-op when that frame's instance count exceeded the buffers (GsAdamFused).  The gate flags are the ones the
+// step's backward left in adam_scratch.
 int trainer_adam(Trainer* t, hipStream_t stream, const float* lr, const int32_t* step, float beta1, float beta2, float eps,
                  bool commit_gate) {
   const int P = t->P;
@@ -76,14 +76,20 @@ int trainer_adam(Trainer* t, hipStream_t stream, const float* lr, const int32_t*
   const float* grads[7] = {t->g_xyz, t->g_fdc, t->g_frest, t->g_opacity, t->g_scaling, t->g_rot, t->g_poses};
   const float* pplr[7] = {t->pplr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (++t->adam_seq == 0u) t->adam_seq = 1u;
-  g_fused.adam_live = t->adam_live; g_fused.adam_seq = t->adam_seq;
+  GsAdamFused fused = {t->adam_live, t->adam_seq, nullptr, 0, nullptr};
   if (commit_gate) {
-    const TilesLayout tl(t->W, t->H);
-    g_fused.commit_count = (const uint32_t*)(t->tiles + tl.start) + tl.T;   // tile_start[T]: the frame's instance count
-    g_fused.commit_capacity = (unsigned long long)t->capacity;
-    g_fused.commit_poison = t->adam_live + 15;   // (words 0..13 are MultiAdamArgs::live's; cleared with them before the first step)
+    fused.commit_count = gs_frame_count(t->tiles, t->W, t->H);
+    fused.commit_capacity = (unsigned long long)t->capacity;
+    fused.commit_poison = t->adam_live + 15;   // (words 0..13 are MultiAdamArgs::live's; cleared with them before the first step)
   }
-  return mi355gs_adam_multi_step(stream, 7, numel, row, params, grads, t->m, t->v, pplr, lr, beta1, beta2, eps, step, t->adam_scratch, nullptr, nullptr, nullptr, 0u);
+  return gs_adam_multi(stream, 7, numel, row, params, grads, t->m, t->v, pplr, lr, beta1, beta2, eps, step, t->adam_scratch, nullptr, nullptr,
+                       nullptr, 0u, &fused);
+}
+
+// the stateless operators' arguments, for raw parameters in the split SH storage (degree 0 reads only the DC coefficient)
+GsScene posed_scene(int P, int D, const float* xyz, const float* f_dc, const float* f_rest, const float* opacity_logit,
+                    const float* log_scales, float scale_modifier, const float* rotation) {
+  return {P, D, D == 0 ? 1 : 16, xyz, f_dc, D == 0 ? nullptr : f_rest, nullptr, opacity_logit, log_scales, rotation, nullptr, scale_modifier};
 }
 
 }  // namespace
@@ -91,7 +97,7 @@ int trainer_adam(Trainer* t, hipStream_t stream, const float* lr, const int32_t*
 extern "C" {
 
 // ---- render() with the pose inside the operator (include/mi355gs.h): the same posed projection kernels the one-call step
-// uses, reached through the same thread-local hook, as two stateless entry points for the autograd binding.
+// uses, as two stateless entry points for the autograd binding.
 int mi355gs_posed_forward_preprocess(void* stream, int P, int D, int W, int H, const float* xyz, const float* f_dc,
                                      const float* f_rest, const float* opacity_logit, const float* log_scales, float scale_modifier,
                                      const float* rotation, const float* pose, const float* view_identity, const float* projmatrix,
@@ -99,11 +105,11 @@ int mi355gs_posed_forward_preprocess(void* stream, int P, int D, int W, int H, c
                                      int32_t* num_rendered, uint8_t* visible, void* grad_scratch, int debug) {
   GS_RANGE();
   if (!pose || D < 0 || D > 3 || (D > 0 && !f_rest)) return MI355GS_EINVAL;
-  struct Scope { ~Scope() { g_fused = GsFusedStepHooks(); } } scope;
-  g_fused.posed.pose = pose;
-  return mi355gs_raster_forward_preprocess(stream, P, D, D == 0 ? 1 : 16, W, H, xyz, f_dc, D == 0 ? nullptr : f_rest, nullptr,
-                                           opacity_logit, log_scales, scale_modifier, rotation, nullptr, view_identity, projmatrix,
-                                           origin, tanfovx, tanfovy, 0, radii, geom, tiles, num_rendered, visible, grad_scratch, debug);
+  GsFrameCtx cx;
+  cx.posed.pose = pose;
+  return gs_frame_project((hipStream_t)stream, posed_scene(P, D, xyz, f_dc, f_rest, opacity_logit, log_scales, scale_modifier, rotation),
+                          {W, H, view_identity, projmatrix, origin, tanfovx, tanfovy}, {geom, tiles, nullptr, 0, radii, grad_scratch, gs_knobs()},
+                          cx, num_rendered, visible, debug);
 }
 
 int mi355gs_posed_backward(void* stream_, int P, int D, int W, int H, const float* bg, const float* xyz, const float* f_dc,
@@ -121,25 +127,21 @@ int mi355gs_posed_backward(void* stream_, int P, int D, int W, int H, const floa
   if (P <= 0)
     return hipMemsetAsync(d_pose, 0, (size_t)(pose_rows > 0 ? pose_rows : 1) * 7 * sizeof(float), stream) == hipSuccess ? MI355GS_OK : MI355GS_ELAUNCH;
   const int rows = (P + 255) / 256;
-  float* gate = (float*)((char*)grad_scratch + mi355gs_raster_grad_gate_offset(P));
-  int rc;
-  {
-    struct Scope { ~Scope() { g_fused = GsFusedStepHooks(); } } scope;
-    g_fused.posed.pose = pose;
-    g_fused.posed.acc = pose_scratch + (size_t)16 * rows;   // unused with `partial` set; kept valid
-    g_fused.posed.partial = pose_scratch;                   // one row of 16 pose sums per projection workgroup
-    // PerPointAdam's whole-tensor gate flags, in the optimizer's group order, from the kernels that write the gradients
-    g_fused.gate = gate; g_fused.gate_tail = true;
-    g_fused.gate_xyz = 0; g_fused.gate_sh = 1; g_fused.gate_sh_rest = 2; g_fused.gate_opacity = 3; g_fused.gate_scaling = 4; g_fused.gate_rot = 5;
-    rc = mi355gs_raster_backward(stream, P, D, D == 0 ? 1 : 16, W, H, bg, xyz, f_dc, D == 0 ? nullptr : f_rest, nullptr, opacity_logit,
-                                 log_scales, scale_modifier, rotation, nullptr, view_identity, projmatrix, origin, tanfovx, tanfovy,
-                                 geom, tiles, binning, capacity, radii, out_color, dL_dpix, grad_scratch, d_xyz, d_means2D, d_f_dc,
-                                 D == 0 ? nullptr : d_f_rest, nullptr, d_opacity_logit, d_log_scales, d_rotation, nullptr,
-                                 grad_scratch_is_clear, debug);
-  }
+  float* gate = (float*)((char*)grad_scratch + gs_grad_gate_offset(P));
+  GsFrameCtx cx;
+  cx.posed.pose = pose;
+  cx.posed.acc = pose_scratch + (size_t)16 * rows;   // unused with `partial` set; kept valid
+  cx.posed.partial = pose_scratch;                   // one row of 16 pose sums per projection workgroup
+  // PerPointAdam's whole-tensor gate flags, in the optimizer's group order, from the kernels that write the gradients
+  cx.gate = gate; cx.gate_tail = true;
+  const GsGradOut o = {d_xyz, d_means2D, d_f_dc, D == 0 ? nullptr : d_f_rest, nullptr, d_opacity_logit, d_log_scales, d_rotation, nullptr};
+  const int rc = gs_frame_backward(stream, posed_scene(P, D, xyz, f_dc, f_rest, opacity_logit, log_scales, scale_modifier, rotation),
+                                   {W, H, view_identity, projmatrix, origin, tanfovx, tanfovy},
+                                   {const_cast<void*>(geom), tiles, const_cast<void*>(binning), capacity, const_cast<int32_t*>(radii), grad_scratch, gs_knobs()},
+                                   cx, bg, out_color, dL_dpix, o, grad_scratch_is_clear != 0, debug);
   if (rc) return rc;
   GS_KRANGE("pose_finish");
-  gs_launch_pose_finish_partials(stream, pose, pose_scratch, rows, d_pose, gate + 6, nullptr, 0, 0.0, 0.f, nullptr, pose_rows, pose_row);
+  gs_launch_pose_finish_partials(stream, pose, pose_scratch, rows, d_pose, gate + GS_GATE_POSE, nullptr, 0, 0.0, 0.f, nullptr, pose_rows, pose_row);
   GS_CHECK_LAUNCH("pose_finish");
   return MI355GS_OK;
 }
@@ -148,7 +150,7 @@ size_t mi355gs_trainer_workspace_bytes(int P, int W, int H, int V, int64_t capac
   if (P < 0 || W <= 0 || H <= 0 || V <= 0 || capacity < 0) return 0;
   Trainer t;
   memset(&t, 0, sizeof(t));
-  t.P = P; t.W = W; t.H = H; t.V = V; t.capacity = capacity;
+  t.P = P; t.W = W; t.H = H; t.V = V; t.capacity = capacity; t.knobs = gs_knobs();
   return carve(t, nullptr);
 }
 
@@ -166,8 +168,7 @@ void* mi355gs_trainer_create(int P, int W, int H, int V, int64_t capacity, float
     t->m[k] = exp_avg[k]; t->v[k] = exp_avg_sq[k];
   }
   t->pplr = per_point_lr;
-  t->min_units = gs_min_units();
-  t->det = gs_deterministic();
+  t->knobs = gs_knobs();
   carve(*t, workspace);
   t->consts_ready = false;
   return t;
@@ -193,59 +194,41 @@ int mi355gs_trainer_step(void* handle, void* stream_, int view, int sh_degree, c
     return MI355GS_EINVAL;
   const int P = t->P, W = t->W, H = t->H;
   if (!t->consts_ready) {
-    GS_KRANGE("trainer_consts");
-    gs_launch_view_consts(stream, t->consts);
-    GS_CHECK_LAUNCH("trainer_consts");
+    if (int rc = gs_write_view_consts(stream, t->consts, "trainer_consts")) return rc;
     // at SH degree 0 f_rest receives no gradient: its (all-zero) gradient buffer is written once here and first
     // touched again when the degree is raised (the backward then rewrites every element each step)
     if (hipMemsetAsync(t->g_frest, 0, (size_t)P * 45 * sizeof(float), stream) != hipSuccess) return MI355GS_ELAUNCH;
     if (hipMemsetAsync(t->adam_live, 0, 16 * sizeof(uint32_t), stream) != hipSuccess) return MI355GS_ELAUNCH;
     t->consts_ready = true;
   }
-  struct HookScope {
-    HookScope(float* gate, const GsPrologue& pro, const GsPosed& posed, int min_units, int det) {
-      gs_pin_min_units(min_units);
-      gs_pin_deterministic(det);
-      g_fused.skip_memsets = true; g_fused.gate = gate; g_fused.prologue = pro; g_fused.posed = posed;
-      g_fused.gate_xyz = 0; g_fused.gate_sh = 1; g_fused.gate_sh_rest = 2; g_fused.gate_opacity = 3; g_fused.gate_scaling = 4; g_fused.gate_rot = 5; g_fused.gate_pose = 6;
-    }
-    ~HookScope() { g_fused = GsFusedStepHooks(); gs_pin_min_units(0); gs_pin_deterministic(-1); }
-  };
-  GsPrologue pro;  // the step's accumulators are cleared by its first kernel (k_pose_fwd)
+  GsPrologue pro;  // the step's accumulators are cleared by its first kernel, the projection
   {
     const TilesLayout tl(W, H);
     pro.grad_records = (float4*)t->grad_scratch; pro.n_vec = (size_t)P * 3;
     pro.tile_counters = (uint32_t*)(t->tiles + tl.count); pro.n_counters = (int)((tl.start - tl.count) / 4);
     pro.g_poses = t->g_poses; pro.n_pose = 7 * t->V; pro.pose_scratch = t->pose_scratch; pro.adam_scratch = t->adam_scratch;
   }
-  GsPosed posed;
-  posed.pose = t->poses + 7 * (size_t)view; posed.acc = t->pose_scratch; posed.partial = t->pose_partial;
-  HookScope hook_scope(t->adam_scratch, pro, posed, t->min_units, t->det);
-  const float* view_m = t->consts;
-  const float* campos = t->consts + 16;
   const float* pose = t->poses + 7 * (size_t)view;
-  int rc;
+  GsFrameCtx cx;
+  cx.prologue = &pro;
+  cx.posed.pose = pose; cx.posed.acc = t->pose_scratch; cx.posed.partial = t->pose_partial;
+  cx.gate = t->adam_scratch;
   // ---- forward: the projection kernel applies the camera-frame transform and the activations itself (GsPosed)
-  // degree 0 reads only the DC coefficient; higher degrees read f_dc + f_rest in place (split storage)
-  const int D = sh_degree, M = D == 0 ? 1 : 16;
-  const float* rest = D == 0 ? nullptr : t->f_rest;
-  float* g_rest = D == 0 ? nullptr : t->g_frest;
-  if ((rc = mi355gs_raster_forward_preprocess(stream, P, D, M, W, H, t->xyz, t->f_dc, rest, nullptr, t->opacity, t->scaling, 1.0f,
-                                              t->rotation, nullptr, view_m, projmatrix, campos, tanfovx, tanfovy, 0, t->radii,
-                                              t->geom, t->tiles, num_rendered_out, nullptr, nullptr, 0)))
-    return rc;
-  if ((rc = mi355gs_raster_forward_render(stream, P, W, H, t->capacity, bg, t->geom, t->tiles, t->binning, t->image, 0))) return rc;
+  const int D = sh_degree;
+  const GsScene scene = posed_scene(P, D, t->xyz, t->f_dc, t->f_rest, t->opacity, t->scaling, 1.0f, t->rotation);
+  const GsView vw = {W, H, t->consts, projmatrix, t->consts + 16, tanfovx, tanfovy};
+  const GsFrameBufs bufs = {t->geom, t->tiles, t->binning, t->capacity, t->radii, t->grad_scratch, t->knobs};
+  int rc;
+  if ((rc = gs_frame_project(stream, scene, vw, bufs, cx, num_rendered_out, nullptr, 0))) return rc;
+  if ((rc = gs_frame_render(stream, P, vw, bufs, bg, t->image, true, 0))) return rc;
   // ---- loss and its gradient in one launch (the SSIM partial-derivative maps never leave LDS); the loss VALUE, which only
   // the host ever reads, is summed from the per-workgroup partials by the single-workgroup pose-finish kernel further down
   if ((rc = gs_loss_fused(stream, 3, H, W, t->image, gt_image, lambda_dssim, t->dL_dimg, t->ssim_scratch))) return rc;
   // ---- backward: down to the raw-parameter gradients and the pose sums in one kernel, then the 7 pose gradients
-  if ((rc = mi355gs_raster_backward(stream, P, D, M, W, H, bg, t->xyz, t->f_dc, rest, nullptr, t->opacity, t->scaling, 1.0f, t->rotation,
-                                    nullptr, view_m, projmatrix, campos, tanfovx, tanfovy, t->geom, t->tiles, t->binning,
-                                    t->capacity, t->radii, t->image, t->dL_dimg, t->grad_scratch, t->g_xyz, t->g_means2D, t->g_fdc,
-                                    g_rest, t->g_colors, t->g_opacity, t->g_scaling, t->g_rot, nullptr, 0, 0)))
-    return rc;
+  const GsGradOut o = {t->g_xyz, t->g_means2D, t->g_fdc, D == 0 ? nullptr : t->g_frest, t->g_colors, t->g_opacity, t->g_scaling, t->g_rot, nullptr};
+  if ((rc = gs_frame_backward(stream, scene, vw, bufs, cx, bg, t->image, t->dL_dimg, o, false, 0))) return rc;
   GS_KRANGE("pose_finish");
-  gs_launch_pose_finish_partials(stream, pose, t->pose_partial, (P + 255) / 256, t->g_poses + 7 * (size_t)view, t->adam_scratch + 6,
+  gs_launch_pose_finish_partials(stream, pose, t->pose_partial, (P + 255) / 256, t->g_poses + 7 * (size_t)view, t->adam_scratch + GS_GATE_POSE,
                                  (const float*)t->ssim_scratch, gs_loss_fused_nblocks(3, H, W), 1.0 / (3.0 * H * W), lambda_dssim, loss_out, 0, 0);
   GS_CHECK_LAUNCH("pose_finish");
   // ---- optimizer: groups in the reference's order xyz, f_dc, f_rest, opacity, scaling, rotation, pose
@@ -259,11 +242,8 @@ int mi355gs_trainer_optimizer_step(void* handle, void* stream_, const float* lr,
   Trainer* t = (Trainer*)handle;
   if (!t || !lr || !step || !t->consts_ready) return MI355GS_EINVAL;  // needs the gradients of a preceding step
   // gate flags of the gradients produced by the preceding mi355gs_trainer_step(..., do_optimizer_step = 0) are still in place
-  g_fused.gate = t->adam_scratch;
   // commit_gate = 0: the caller has seen the count; 1: it has not — the launch decides on the device like a one-call step's
-  const int rc = trainer_adam(t, (hipStream_t)stream_, lr, step, beta1, beta2, eps, commit_gate != 0);
-  g_fused = GsFusedStepHooks();
-  return rc;
+  return trainer_adam(t, (hipStream_t)stream_, lr, step, beta1, beta2, eps, commit_gate != 0);
 }
 
 }  // extern "C"
