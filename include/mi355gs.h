@@ -497,6 +497,27 @@ int mi355gs_path_render(void* path, void* stream, int sh_degree, const float* pr
                         const float* bg, const float* poses, int first, int n, uint8_t* frames, int32_t* counts);
 void mi355gs_path_destroy(void* path);
 
+/* ----------------------------------------------------------------------------------------------
+ * Evaluation of 8-bit frame sets (reference metrics.py:60-70 on the images utils/sfm_utils.py:452-462 `readImages` loads):
+ * a, b: N pairs of interleaved frames, uint8 [N][H][W][3] each, in device memory (no alignment is required of the bases:
+ * a slice of a stack of odd-sized frames is fine).  Per pair i
+ *   sq_sum[i]    = sum over the 3 H W byte pairs of (a - b)^2, an exact integer (32-bit partial sums per workgroup, finished
+ *                  in 64 bits): psnr's mse (utils/image_utils.py:17-19) is sq_sum / (65025 * 3 H W);
+ *   ssim_mean[i] = utils/loss_utils.py:55-85 `ssim` of the pair as torchvision's to_tensor hands it over: x = byte / 255 as a
+ *                  correctly rounded fp32 quotient, 11x11 Gaussian window (sigma 1.5), zero "same" padding, C1 = 0.01^2,
+ *                  C2 = 0.03^2, mean over 3 H W (float partial sums per workgroup, finished per pair in a fixed order in double).
+ *                  A window whose moments are bit-equal in both frames counts exactly 1: identical pairs, all-black ones
+ *                  included, give sq_sum = 0 and ssim_mean = 1.0f exactly.
+ * Two launches per call whatever N is (one over all 32x16 tiles of all pairs, 6 bytes read per pixel pair, and one finishing
+ * launch), on the caller's stream; no host synchronisation, no allocation, no memset.  scratch: the scratch-size query's bytes of
+ * device memory, owned by the caller (0 = the sizes are refused).  sq_sum, ssim_mean: device arrays of N.
+ * Limits (MI355GS_EINVAL beyond them, as for null pointers and non-positive sizes): N <= 65535, H <= 1048560,
+ * 3 H W <= 2^31 - 1 (a byte's offset inside a frame is an int), N x ceil(H / 16) x ceil(W / 32) <= 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_metrics_rgb8_scratch_bytes(int N, int H, int W);
+int mi355gs_metrics_rgb8(void* stream, int N, int H, int W, const uint8_t* a, const uint8_t* b, void* scratch, int64_t* sq_sum,
+                         float* ssim_mean);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,8 @@ _SIGNATURES = {
     "mi355gs_path_create": (c_void_p, [c_int, c_int, c_int, c_int, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "mi355gs_path_render": (c_int, [_P, _P, c_int, _P, c_float, c_float, _P, _P, c_int, c_int, _P, _P]),
     "mi355gs_path_destroy": (None, [_P]),
+    "mi355gs_metrics_rgb8_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355gs_metrics_rgb8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

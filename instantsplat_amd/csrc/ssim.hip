@@ -641,6 +641,198 @@ __global__ __launch_bounds__(1024) void k_loss_program_grad(GsLossProgram p, int
   loss_pair_bwd_four(n, ((long long)(blockIdx.x - 1) * 1024 + threadIdx.x) * 4, a, b, dssim, sl, ss, use_l1, use_ss, d_a);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Evaluation of 8-bit frame sets (include/mi355gs.h, mi355gs_metrics_rgb8): per pair of interleaved [H][W][3] byte frames the
+// exact integer sum of squared differences (reference utils/image_utils.py:17-19, psnr's mse times 65025 * 3HW) and the mean SSIM
+// of reference metrics.py:67 -> utils/loss_utils.py:55-85 on `to_tensor` inputs (byte / 255 in fp32).  Forward only, so nothing
+// is written per pixel: a workgroup reads 6 B per pixel pair (+ halo) and leaves 8 bytes.
+//
+// One workgroup = one 32x16 output tile of one frame pair, all three channels.  The 42x26 pixel halo of both frames (126 bytes
+// per staged row and frame) is read ONCE from the interleaved bytes, converted through a 256-entry table of correctly rounded
+// quotients b / 255 (one IEEE division per thread; b * (1/255) differs in the last bit for 126 of the 256 values) and de-interleaved
+// into three float planes per frame in LDS; the squared byte differences of the tile's own pixels are summed on the way, in
+// integers.  The two window passes of k_ssim_fwd then run once per channel over those planes.
+// Loads: the rows of a W x 3 byte image start at any byte, and so may the frames (a slice of a stack of odd-sized frames).  With
+// W a multiple of 4 and both bases 4-byte aligned — uniform over the launch, decided on the host — every row and every tile's first
+// byte (96 bytes per tile column) is 4-byte aligned, and a staged row is the 32 words from 16 bytes before the tile's first byte;
+// a word lies wholly inside or wholly outside its image row.  Otherwise plain byte loads, as k_rgb8_from_planar.
+constexpr int MB_ROW_BYTES = THX * 3;                          // 126 bytes of a staged row per frame
+constexpr int MB_ROW_WORDS = 32;                               // aligned path: bytes [3 ox - 16, 3 ox + 112) cover [3 ox - 15, 3 ox + 111)
+constexpr int MB_BYTE_ITERS = (TH * MB_ROW_BYTES + 255) / 256;  // 13
+constexpr int MB_WORD_ITERS = (TH * MB_ROW_WORDS + 255) / 256;  // 4
+static_assert(MB_ROW_WORDS * 4 >= MB_ROW_BYTES + 1 && (TSX * 3) % 4 == 0, "a staged row fits the aligned words");
+
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ uint32_t mb_dpp_u32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);   // lanes without a source read 0
+}
+// integer forms of gs_wave_sum_row3 / gs_wave_sum_row3_f64: the total lands in lanes 48..63
+__device__ __forceinline__ uint32_t mb_wave_sum_row3_u32(uint32_t v) {
+  v += mb_dpp_u32<0xB1>(v);
+  v += mb_dpp_u32<0x4E>(v);
+  v += mb_dpp_u32<0x141>(v);
+  v += mb_dpp_u32<0x140>(v);
+  v += mb_dpp_u32<0x142, 0xA>(v);
+  v += mb_dpp_u32<0x143, 0xC>(v);
+  return v;
+}
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ unsigned long long mb_dpp_u64(unsigned long long v) {
+  return ((unsigned long long)mb_dpp_u32<CTRL, ROW_MASK>((uint32_t)(v >> 32)) << 32) | mb_dpp_u32<CTRL, ROW_MASK>((uint32_t)v);
+}
+__device__ __forceinline__ unsigned long long mb_wave_sum_row3_u64(unsigned long long v) {
+  v += mb_dpp_u64<0xB1>(v);
+  v += mb_dpp_u64<0x4E>(v);
+  v += mb_dpp_u64<0x141>(v);
+  v += mb_dpp_u64<0x140>(v);
+  v += mb_dpp_u64<0x142, 0xA>(v);
+  v += mb_dpp_u64<0x143, 0xC>(v);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_metrics_rgb8(int H, int W, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                      float* __restrict__ part_ssim, uint32_t* __restrict__ part_sq, int aligned) {
+  __shared__ float s_lut[256];
+  __shared__ float s_x[3][TH][SXP];
+  __shared__ float s_y[3][TH][SXP];
+  __shared__ gs_v2f s_h[5][TH][TS];  // row-pass results of one channel, columns (c, c + 16) as one pair
+  __shared__ float s_red[4];
+  __shared__ uint32_t s_redu[4];
+  const int tid = threadIdx.y * TS + threadIdx.x;
+  const int ox = blockIdx.x * TSX, oy = blockIdx.y * TS;
+  const int row_bytes = 3 * W;   // 3 H W fits an int (checked by the entry point)
+  const size_t frame = (size_t)blockIdx.z * (size_t)H * (size_t)row_bytes;
+  const uint8_t* __restrict__ pa = a + frame;
+  const uint8_t* __restrict__ pb = b + frame;
+  s_lut[tid] = (float)tid / 255.0f;   // torch's div: the correctly rounded quotient
+  uint32_t sq = 0;
+  // Staging: every load goes to a clamped (always valid) address and is issued before the barrier that publishes the table, so a
+  // thread waits for HBM/L2 once (see k_ssim_fwd); what lies outside the image is staged as 0 ("same" padding with zeros).
+  if (aligned) {
+    uint32_t va[MB_WORD_ITERS], vb[MB_WORD_ITERS];
+#pragma unroll
+    for (int j = 0; j < MB_WORD_ITERS; ++j) {
+      const int i = tid + 256 * j, r = min(i >> 5, TH - 1), w = i & 31;
+      const int gy = min(max(oy + r - HALO, 0), H - 1), off = min(max(3 * ox - 16 + 4 * w, 0), row_bytes - 4);
+      const size_t o = (size_t)gy * row_bytes + off;   // a multiple of 4
+      va[j] = *reinterpret_cast<const uint32_t*>(pa + o); vb[j] = *reinterpret_cast<const uint32_t*>(pb + o);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MB_WORD_ITERS; ++j) {
+      const int i = tid + 256 * j, r = i >> 5, w = i & 31;
+      if (i >= TH * MB_ROW_WORDS) break;
+      const int gy = oy + r - HALO, off = 3 * ox - 16 + 4 * w;
+      const bool in = gy >= 0 && gy < H && off >= 0 && off < row_bytes;
+      const uint32_t wa = in ? va[j] : 0u, wb = in ? vb[j] : 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int p = 4 * w + k - 1;   // byte of the staged row: p = 3 * column + channel
+        if (p < 0 || p >= MB_ROW_BYTES) continue;
+        const int c = p / 3, ch = p - 3 * c;
+        const uint32_t ba = (wa >> (8 * k)) & 255u, bb = (wb >> (8 * k)) & 255u;
+        s_x[ch][r][c] = s_lut[ba]; s_y[ch][r][c] = s_lut[bb];
+        if (r >= HALO && r < HALO + TS && c >= HALO && c < HALO + TSX) { const int d = (int)ba - (int)bb; sq += (uint32_t)(d * d); }
+      }
+    }
+  } else {
+    uint8_t va[MB_BYTE_ITERS], vb[MB_BYTE_ITERS];
+#pragma unroll
+    for (int j = 0; j < MB_BYTE_ITERS; ++j) {
+      const int i = tid + 256 * j, r = min(i / MB_ROW_BYTES, TH - 1), p = i - (i / MB_ROW_BYTES) * MB_ROW_BYTES;
+      const int gy = min(max(oy + r - HALO, 0), H - 1), off = min(max(3 * (ox - HALO) + p, 0), row_bytes - 1);
+      const size_t o = (size_t)gy * row_bytes + off;
+      va[j] = pa[o]; vb[j] = pb[o];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MB_BYTE_ITERS; ++j) {
+      const int i = tid + 256 * j, r = i / MB_ROW_BYTES, p = i - r * MB_ROW_BYTES;
+      if (i >= TH * MB_ROW_BYTES) break;
+      const int gy = oy + r - HALO, off = 3 * (ox - HALO) + p;
+      const bool in = gy >= 0 && gy < H && off >= 0 && off < row_bytes;
+      const int c = p / 3, ch = p - 3 * c;
+      const uint32_t ba = in ? (uint32_t)va[j] : 0u, bb = in ? (uint32_t)vb[j] : 0u;
+      s_x[ch][r][c] = s_lut[ba]; s_y[ch][r][c] = s_lut[bb];
+      if (r >= HALO && r < HALO + TS && c >= HALO && c < HALO + TSX) { const int d = (int)ba - (int)bb; sq += (uint32_t)(d * d); }
+    }
+  }
+  __syncthreads();
+  const int ly = threadIdx.y, lx = threadIdx.x;
+  const int gy = oy + ly;
+  float val = 0.f;
+  for (int ch = 0; ch < 3; ++ch) {
+    if (ch) __syncthreads();   // the column pass of the channel before has read s_h
+    for (int i = tid; i < ROW_ITEMS; i += 256) {
+      const int r = i >> 4, c = i & 15;
+      gs_v2f sx = {0.f, 0.f}, sy = sx, sxx = sx, syy = sx, sxy = sx;
+#pragma unroll
+      for (int k = 0; k < 11; ++k) {
+        const gs_v2f w = {gw(k), gw(k)};
+        const gs_v2f x = {s_x[ch][r][c + k], s_x[ch][r][c + TS + k]}, y = {s_y[ch][r][c + k], s_y[ch][r][c + TS + k]};
+        const gs_v2f wx = w * x, wy = w * y;
+        sx = gs_fma2(w, x, sx); sy = gs_fma2(w, y, sy);
+        sxx = gs_fma2(wx, x, sxx); syy = gs_fma2(wy, y, syy); sxy = gs_fma2(wx, y, sxy);
+      }
+      s_h[0][r][c] = sx; s_h[1][r][c] = sy; s_h[2][r][c] = sxx; s_h[3][r][c] = syy; s_h[4][r][c] = sxy;
+    }
+    __syncthreads();
+    gs_v2f mu1 = {0.f, 0.f}, mu2 = mu1, exx = mu1, eyy = mu1, exy = mu1;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) {
+      const gs_v2f w = {gw(k), gw(k)};
+      mu1 = gs_fma2(w, s_h[0][ly + k][lx], mu1); mu2 = gs_fma2(w, s_h[1][ly + k][lx], mu2);
+      exx = gs_fma2(w, s_h[2][ly + k][lx], exx); eyy = gs_fma2(w, s_h[3][ly + k][lx], eyy);
+      exy = gs_fma2(w, s_h[4][ly + k][lx], exy);
+    }
+    const gs_v2f two = {2.f, 2.f}, c1 = {C1, C1}, c2 = {C2, C2};
+    const gs_v2f mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+    const gs_v2f s1 = exx - mu1_sq, s2 = eyy - mu2_sq, s12 = exy - mu12;
+    const gs_v2f A = mu1_sq + mu2_sq + c1, B = s1 + s2 + c2, Cc = two * mu12 + c1, Dd = two * s12 + c2;
+    const gs_v2f invA = {ssim_rcp(A[0]), ssim_rcp(A[1])}, invB = {ssim_rcp(B[0]), ssim_rcp(B[1])};
+    const gs_v2f m = Cc * Dd * (invA * invB);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      // A window whose five moments are bit-equal for the two frames has SSIM exactly 1 (A = C and B = D); the formula gets there
+      // only to the reciprocals' ulp.  Nothing is differentiated here, so the all-zero window takes the exact value too (cf.
+      // ssim_equal_window): a pair of identical frames, black ones included, scores 1.0f exactly.
+      const bool same = mu1[half] == mu2[half] && exx[half] == eyy[half] && exx[half] == exy[half];
+      if (ox + lx + half * TS < W && gy < H) val += same ? 1.f : m[half];
+    }
+  }
+  val = gs_wave_sum_row3(val);   // the totals are in lane 63
+  sq = mb_wave_sum_row3_u32(sq);  // at most 512 x 3 x 65025 per workgroup: 32 bits hold it
+  const int wave = tid >> 6, lane = tid & 63;
+  if (lane == 63) { s_red[wave] = val; s_redu[wave] = sq; }
+  __syncthreads();
+  if (tid == 0) {
+    const size_t t = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    part_ssim[t] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    part_sq[t] = (s_redu[0] + s_redu[1]) + (s_redu[2] + s_redu[3]);
+  }
+}
+
+// One workgroup per frame pair: its tiles' partial sums in a fixed order, the SSIM sum in double (as k_ssim_finish), the squared
+// differences in 64-bit integers.
+__global__ __launch_bounds__(256) void k_metrics_rgb8_finish(int tiles, double n, const float* __restrict__ part_ssim,
+                                                             const uint32_t* __restrict__ part_sq, int64_t* __restrict__ sq_sum,
+                                                             float* __restrict__ ssim_mean) {
+  __shared__ double s_a[4];
+  __shared__ unsigned long long s_q[4];
+  const size_t base = (size_t)blockIdx.x * (size_t)tiles;
+  double acc = 0.0;
+  unsigned long long q = 0;
+  for (int i = threadIdx.x; i < tiles; i += 256) { acc += (double)part_ssim[base + i]; q += part_sq[base + i]; }
+  acc = gs_wave_sum_row3_f64(acc); q = mb_wave_sum_row3_u64(q);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 63) { s_a[wave] = acc; s_q[wave] = q; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    ssim_mean[blockIdx.x] = (float)((((s_a[0] + s_a[1]) + s_a[2]) + s_a[3]) / n);   // (n / n is exactly 1)
+    sq_sum[blockIdx.x] = (int64_t)(((s_q[0] + s_q[1]) + s_q[2]) + s_q[3]);
+  }
+}
+
 }  // namespace
 
 static inline int l1_nblocks(long long n) { return (int)((n + L1_THREADS * L1_PER_THREAD - 1) / (L1_THREADS * L1_PER_THREAD)); }
@@ -836,6 +1028,39 @@ int mi355gs_loss_program_eval_grad(void* stream_, int n_ops, const int32_t* ops,
                      1.0 / (double)n, (const float*)scratch, ssim_mean, l1_mean, out, host_out, ticket, n, img1, img2, dssim_dimg1, c_l1, c_ssim,
                      (float)n, d_img1);
   GS_CHECK_LAUNCH("loss_program_grad");
+  return MI355GS_OK;
+}
+
+// N <= 65535 (grid z), H <= 65535 * 16 (grid y), 3 H W <= INT32_MAX (byte offsets inside a frame are ints), N x tiles <= INT32_MAX
+static inline bool metrics_rgb8_size_ok(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0 || N > 65535 || H > 65535 * TS) return false;
+  if ((long long)H * W > 0x7fffffffLL / 3) return false;
+  return (long long)N * ssim_nblocks(1, 1, H, W) <= 0x7fffffffLL;
+}
+
+size_t mi355gs_metrics_rgb8_scratch_bytes(int N, int H, int W) {
+  if (!metrics_rgb8_size_ok(N, H, W)) return 0;
+  return 2 * gs_align((size_t)N * ssim_nblocks(1, 1, H, W) * sizeof(float));
+}
+
+int mi355gs_metrics_rgb8(void* stream_, int N, int H, int W, const uint8_t* a, const uint8_t* b, void* scratch, int64_t* sq_sum,
+                         float* ssim_mean) {
+  GS_RANGE();
+  hipStream_t stream = (hipStream_t)stream_;
+  const int debug = 0;
+  if (!metrics_rgb8_size_ok(N, H, W) || !a || !b || !scratch || !sq_sum || !ssim_mean) return MI355GS_EINVAL;
+  const int tiles = ssim_nblocks(1, 1, H, W);
+  float* part_ssim = (float*)scratch;
+  uint32_t* part_sq = (uint32_t*)((char*)scratch + gs_align((size_t)N * tiles * sizeof(float)));
+  const int aligned = (W % 4 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 3) == 0);
+  const dim3 grid((W + TSX - 1) / TSX, (H + TS - 1) / TS, N);
+  GS_KRANGE("metrics_rgb8");
+  hipLaunchKernelGGL(k_metrics_rgb8, grid, dim3(TS, TS), 0, stream, H, W, a, b, part_ssim, part_sq, aligned);
+  GS_CHECK_LAUNCH("metrics_rgb8");
+  GS_KRANGE("metrics_rgb8_finish");
+  hipLaunchKernelGGL(k_metrics_rgb8_finish, dim3(N), dim3(256), 0, stream, tiles, 3.0 * (double)H * (double)W, (const float*)part_ssim,
+                     (const uint32_t*)part_sq, sq_sum, ssim_mean);
+  GS_CHECK_LAUNCH("metrics_rgb8_finish");
   return MI355GS_OK;
 }
 

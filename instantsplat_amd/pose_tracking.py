@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
 import time
 from typing import List
 
@@ -236,6 +237,39 @@ def render_set_optimize(views: List, gaussians, pipe, background, num_iter: int 
     for i, view in enumerate(views):
         out.append(track(view, gaussians, pipe, background, None if init_poses is None else init_poses[i], num_iter))
     return out
+
+
+def render_test_set(model_path, iteration, views: List, gaussians, pipe, background, num_iter: int = 500, fused: bool = True,
+                    init_poses=None) -> dict:
+    """The file-writing form of reference render.py:99-170: every view tracked by `render_set_optimize`, its final render and
+    `view.original_image[0:3]` quantised as torchvision.utils.save_image does (render_path.quantize_rgb8) and written to
+    <model_path>/test/ours_<iteration>/renders/<image_name>.png and .../gt/<image_name>.png.
+    -> dict(results = the tracker's per-view dicts,
+            frames = {"ours_<iteration>": [dict(names = file names, renders = uint8 [n,H,W,3], gts = uint8 [n,H,W,3]), ...]}:
+            the two frame stacks as device tensors, one entry per image size — what `metrics.evaluate(model_path, frames=...)`
+            scores without reading the files back)."""
+    from .render_path import _save_png, quantize_rgb8
+    views = list(views)
+    method = f"ours_{iteration}"
+    base = os.path.join(str(model_path), "test", method)
+    render_dir, gts_dir = os.path.join(base, "renders"), os.path.join(base, "gt")
+    os.makedirs(render_dir, exist_ok=True)
+    os.makedirs(gts_dir, exist_ok=True)
+    results = render_set_optimize(views, gaussians, pipe, background, num_iter=num_iter, init_poses=init_poses, fused=fused)
+    dev = gaussians.get_xyz.device
+    by_size = {}
+    for view, res in zip(views, results):
+        name = f"{view.image_name}.png"
+        render8 = quantize_rgb8(res["render"].detach().float().contiguous())
+        gt8 = quantize_rgb8(view.original_image[0:3].to(dev).float().contiguous())
+        grp = by_size.setdefault(tuple(render8.shape), dict(names=[], renders=[], gts=[]))
+        grp["names"].append(name); grp["renders"].append(render8); grp["gts"].append(gt8)
+    groups = [dict(names=g["names"], renders=torch.stack(g["renders"]), gts=torch.stack(g["gts"])) for g in by_size.values()]
+    for g in groups:   # one device-to-host copy per stack
+        for stack, d in ((g["renders"], render_dir), (g["gts"], gts_dir)):
+            for name, frame in zip(g["names"], stack.cpu().numpy()):
+                _save_png(os.path.join(d, name), frame)
+    return dict(results=results, frames={method: groups})
 
 
 def measure_fps(view, gaussians, pipe, background, pose, frames: int = 1000) -> dict:
