@@ -192,13 +192,21 @@ struct CamParams {  // passed by value (kernarg): wave-uniform, lives in SGPRs
   int W, H, gx, gy;
 };
 
-// DPP (data-parallel primitive) lane exchange: one VALU op, no LDS traffic.
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ float gs_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
+// DPP (data-parallel primitive) lane exchange of a 32- or 64-bit value (two moves): VALU ops, no LDS traffic.  Lanes without a
+// source read zero bits.
+template <int CTRL, int ROW_MASK = 0xF, class T>
+__device__ __forceinline__ T gs_dpp(T v) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two 32-bit moves");
+  uint32_t w[sizeof(T) / 4];
+  __builtin_memcpy(w, &v, sizeof(T));
+  for (size_t i = 0; i < sizeof(T) / 4; ++i) w[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[i], CTRL, ROW_MASK, 0xF, false);
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
 }
-// wave64 sum in 6 DPP adds; the total lands in lanes 48..63 (the last row of 16). All lanes must be active.
-__device__ __forceinline__ float gs_wave_sum_row3(float v) {
+// wave64 sum in 6 DPP adds (a shuffle butterfly is six LDS-crossbar round trips, twelve for 64 bits); the total lands in lanes
+// 48..63 (the last row of 16).  All lanes must be active.
+template <class T>
+__device__ __forceinline__ T gs_wave_sum_row3(T v) {
   v += gs_dpp<0xB1>(v);        // quad_perm [1,0,3,2]
   v += gs_dpp<0x4E>(v);        // quad_perm [2,3,0,1]
   v += gs_dpp<0x141>(v);       // row_half_mirror
@@ -207,23 +215,26 @@ __device__ __forceinline__ float gs_wave_sum_row3(float v) {
   v += gs_dpp<0x143, 0xC>(v);  // row_bcast:31 into rows 2,3 -> row 3 holds the wave total
   return v;
 }
+__device__ __forceinline__ double gs_wave_sum_row3_f64(double v) { return gs_wave_sum_row3(v); }
 
-// the same for a double (two 32-bit DPP moves per step): the total lands in lanes 48..63
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ double gs_dpp_f64(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, 0xF, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xF, false);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));   // lanes without a source read +0.0
+// Two means from [nblocks, 2] float partial sums, for a workgroup of 1024 threads: double accumulation in a fixed order (strided
+// per thread, DPP wave sum, the 16 wave totals in sequence), so every kernel that finishes the same partials leaves the same
+// bits.  The results are valid in thread 0 only.
+__device__ __forceinline__ void gs_finish_two_means(int nblocks, double inv_n, const float* __restrict__ partial, float& mean0, float& mean1) {
+  __shared__ double s_a[16], s_b[16];
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 1024) { a += (double)partial[2 * i]; b += (double)partial[2 * i + 1]; }
+  a = gs_wave_sum_row3(a); b = gs_wave_sum_row3(b);
+  if ((threadIdx.x & 63) == 63) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double ta = 0.0, tb = 0.0;
+  for (int w = 0; w < 16; ++w) { ta += s_a[w]; tb += s_b[w]; }
+  mean0 = (float)(ta * inv_n); mean1 = (float)(tb * inv_n);
 }
-__device__ __forceinline__ double gs_wave_sum_row3_f64(double v) {
-  v += gs_dpp_f64<0xB1>(v);
-  v += gs_dpp_f64<0x4E>(v);
-  v += gs_dpp_f64<0x141>(v);
-  v += gs_dpp_f64<0x140>(v);
-  v += gs_dpp_f64<0x142, 0xA>(v);
-  v += gs_dpp_f64<0x143, 0xC>(v);
-  return v;
+// the training loss from the two means (reference train.py:176)
+__device__ __forceinline__ float gs_l1_ssim_loss(float lambda_dssim, float l1_mean, float ssim_mean) {
+  return (1.0f - lambda_dssim) * l1_mean + lambda_dssim * (1.0f - ssim_mean);
 }
 
 // Two floats in an aligned VGPR pair: element-wise arithmetic on it compiles to CDNA3/4's full-rate packed-FP32 ops

@@ -128,17 +128,9 @@ __global__ __launch_bounds__(1024) void k_pose_finish_partials(const float* __re
   // loss VALUE (reference train.py:176; only ever read by the host) — in a fixed order, double accumulation — instead of a
   // finishing launch of its own.
   if (loss) {
-    __shared__ double s_la[16], s_lb[16];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < loss_nblocks; i += 1024) { a += (double)loss_partial[2 * i]; b += (double)loss_partial[2 * i + 1]; }
-    a = gs_wave_sum_row3_f64(a); b = gs_wave_sum_row3_f64(b);   // DPP: a 64-bit shuffle butterfly is twelve LDS-crossbar round trips per value
-    if ((threadIdx.x & 63) == 63) { s_la[threadIdx.x >> 6] = a; s_lb[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double ta = 0.0, tb = 0.0;
-      for (int w = 0; w < 16; ++w) { ta += s_la[w]; tb += s_lb[w]; }
-      *loss = (1.0f - lambda_dssim) * (float)(tb * loss_inv_n) + lambda_dssim * (1.0f - (float)(ta * loss_inv_n));
-    }
+    float ssim_mean, l1_mean;
+    gs_finish_two_means(loss_nblocks, loss_inv_n, loss_partial, ssim_mean, l1_mean);
+    if (threadIdx.x == 0) *loss = gs_l1_ssim_loss(lambda_dssim, l1_mean, ssim_mean);
   }
   // a wave holds four row groups (its four rows of 16 lanes): add them with the row swaps, then 16 waves x 16 sums through LDS
   const float wsum = gs_sum_rows((v0 + v1) + (v2 + v3));

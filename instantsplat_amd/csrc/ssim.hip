@@ -22,7 +22,6 @@ constexpr int TH = TS + 2 * HALO;    // 26 input rows per tile
 constexpr int THX = TSX + 2 * HALO;  // 42 input columns per tile
 constexpr int SXP = 48;              // staged row stride in floats: the four rows a wave reads at once (16 lanes each) fall into
                                      // disjoint 16-bank groups (48 = 16 mod 32 ... 0, 48, 96, 144 -> banks 0, 48, 32, 16)
-constexpr int STAGE_ITERS = (TH * SXP + 255) / 256;  // 5
 constexpr int ROW_ITEMS = TH * TS;   // row-pass work items: (staged row, column pair)
 constexpr float C1 = 0.01f * 0.01f;
 constexpr float C2 = 0.03f * 0.03f;
@@ -43,13 +42,118 @@ __device__ __forceinline__ float gw(int k) {
 // (x = y and c = -2 b) instead of an fma's rounding residual.  Windows that are zero in both images (exx = 0: an empty background)
 // are left to the formula: its d1 is exactly 0 there, and the backward's x and y factors are 0.  Every window and pixel but the
 // nonzero equal ones keeps the formula's own bits.
-__device__ __forceinline__ bool ssim_equal_window(float mu1, float mu2, float exx, float eyy, float exy) {
-  return mu1 == mu2 && exx == eyy && exx == exy && exx != 0.f;
+// zero_counts: the caller differentiates nothing (k_metrics_rgb8), so the all-zero window takes the exact value too — a pair of
+// identical frames, black ones included, scores 1.0f exactly.
+__device__ __forceinline__ bool ssim_equal_window(float mu1, float mu2, float exx, float eyy, float exy, bool zero_counts) {
+  return mu1 == mu2 && exx == eyy && exx == exy && (zero_counts || exx != 0.f);
 }
 
 __device__ __forceinline__ float ssim_rcp(float x) {
   const float r = __builtin_amdgcn_rcpf(x);
   return fmaf(fmaf(-x, r, 1.0f), r, r);
+}
+__device__ __forceinline__ gs_v2f ssim_rcp(gs_v2f x) { return gs_v2f{ssim_rcp(x[0]), ssim_rcp(x[1])}; }
+
+// The SSIM window arithmetic on T = float (one window) or gs_v2f (two windows, packed FP32; the per-component arithmetic is the
+// scalar one): from the five moments to the SSIM value m, its partial derivatives d1 = dm/dmu1, d2 = dm/dsigma1^2,
+// d3 = dm/dsigma12, and 1 / B for the equal-window rule, which the caller applies per window (ssim_exact).  A caller that
+// ignores d1..d3 does not pay for them.
+template <class T> struct SsimWindow { T m, d1, d2, d3, invB; };
+__device__ __forceinline__ float ssim_lane(float v, int) { return v; }
+__device__ __forceinline__ float ssim_lane(gs_v2f v, int h) { return v[h]; }
+// mu1^2 + mu2^2, rounded as the two forms always were (which product is fused shows in the last bits of every output): the scalar
+// form adds the two rounded squares; the packed form fuses the SECOND square, v_pk_fma_f32(mu2, mu2, mu1^2).  With two
+// contractable products in one sum the choice is the compiler's and moves with the code around it, so the device build names the
+// fusion; the emulator's gs_fma2 rounds twice everywhere.
+__device__ __forceinline__ float ssim_sum_sq(float mu1_sq, float, float mu2_sq) { return mu1_sq + mu2_sq; }
+__device__ __forceinline__ gs_v2f ssim_sum_sq(gs_v2f mu1_sq, gs_v2f mu2, gs_v2f mu2_sq) {
+#ifdef __clang__
+  return __builtin_elementwise_fma(mu2, mu2, mu1_sq);
+#else
+  return mu1_sq + mu2_sq;
+#endif
+}
+template <class T>
+__device__ __forceinline__ T ssim_all(float v) {   // v in every lane
+  if constexpr (std::is_same<T, float>::value) return v;
+  else return T{v, v};
+}
+template <class T>
+__device__ __forceinline__ SsimWindow<T> ssim_window(T mu1, T mu2, T exx, T eyy, T exy) {
+  const T two = ssim_all<T>(2.f), c1 = ssim_all<T>(C1), c2 = ssim_all<T>(C2);
+  const T mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+  const T s1 = exx - mu1_sq, s2 = eyy - mu2_sq, s12 = exy - mu12;
+  const T A = ssim_sum_sq(mu1_sq, mu2, mu2_sq) + c1, B = s1 + s2 + c2, Cc = two * mu12 + c1, Dd = two * s12 + c2;
+  // two reciprocals per pixel (v_rcp_f32 + one Newton step: <= 1 ulp) instead of four IEEE divisions (~10 VALU ops each)
+  const T invA = ssim_rcp(A), invB = ssim_rcp(B), invAB = invA * invB;
+  const T m = Cc * Dd * invAB;
+  const T t = mu1 * two * Cc * Dd * invAB;
+  const T d1 = (mu2 * two * Dd) * invAB - (mu2 * two * Cc) * invAB - t * invA + t * invB;
+  const T d2 = -m * invB;
+  const T d3 = two * Cc * invAB;
+  return {m, d1, d2, d3, invB};
+}
+// window `h` of a pair (or the window, h = 0) with the equal-window rule applied
+template <class T>
+__device__ __forceinline__ SsimWindow<float> ssim_exact(const SsimWindow<T>& w, int h, bool same) {
+  const float invB = ssim_lane(w.invB, h);
+  return {same ? 1.f : ssim_lane(w.m, h), same ? 0.f : ssim_lane(w.d1, h), same ? -invB : ssim_lane(w.d2, h),
+          same ? 2.f * invB : ssim_lane(w.d3, h), invB};
+}
+
+// Staging of N planes' 26 x 42 halo of the 32x16 tile (zero outside the image): every load goes to a clamped (always valid) address
+// and is issued before the first LDS write, so a thread waits for HBM/L2 once — as a loop of predicated loads this was ten
+// dependent round trips per thread and most of k_ssim_fwd's duration.
+template <int N>
+__device__ __forceinline__ void ssim_tile_stage(int tid, int H, int W, int ox, int oy, const float* const (&src)[N], float (*const (&dst)[N])[SXP]) {
+  constexpr int ITERS = (TH * SXP + 255) / 256;  // 5
+  float v[N][ITERS];
+#pragma unroll
+  for (int j = 0; j < ITERS; ++j) {
+    const int i = tid + 256 * j, r = i / SXP, c = i - r * SXP;
+    const size_t o = (size_t)min(max(oy + r - HALO, 0), H - 1) * W + min(max(ox + c - HALO, 0), W - 1);
+#pragma unroll
+    for (int p = 0; p < N; ++p) v[p][j] = src[p][o];
+  }
+#pragma unroll
+  for (int j = 0; j < ITERS; ++j) {
+    const int i = tid + 256 * j, r = i / SXP, c = i - r * SXP;
+    const int gy = oy + r - HALO, gx = ox + c - HALO;
+    const bool in = c < THX && gy >= 0 && gy < H && gx >= 0 && gx < W;
+    if (i < TH * SXP) {
+#pragma unroll
+      for (int p = 0; p < N; ++p) dst[p][r][c] = in ? v[p][j] : 0.f;
+    }
+  }
+}
+
+// Row pass of the 32x16 tile: the five moments of the staged x and y (11 taps along the rows) for every (staged row, column pair)
+__device__ __forceinline__ void ssim_tile_row_pass(int tid, const float (*s_x)[SXP], const float (*s_y)[SXP], gs_v2f (*s_h)[TH][TS]) {
+  for (int i = tid; i < ROW_ITEMS; i += 256) {
+    const int r = i >> 4, c = i & 15;
+    gs_v2f sx = {0.f, 0.f}, sy = sx, sxx = sx, syy = sx, sxy = sx;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) {
+      const gs_v2f w = {gw(k), gw(k)};
+      const gs_v2f x = {s_x[r][c + k], s_x[r][c + TS + k]}, y = {s_y[r][c + k], s_y[r][c + TS + k]};
+      const gs_v2f wx = w * x, wy = w * y;
+      sx = gs_fma2(w, x, sx); sy = gs_fma2(w, y, sy);
+      sxx = gs_fma2(wx, x, sxx); syy = gs_fma2(wy, y, syy); sxy = gs_fma2(wx, y, sxy);
+    }
+    s_h[0][r][c] = sx; s_h[1][r][c] = sy; s_h[2][r][c] = sxx; s_h[3][r][c] = syy; s_h[4][r][c] = sxy;
+  }
+}
+// Column pass of the 32x16 tile: the thread's column pair of N row-pass maps, 11 taps down the rows
+template <int N>
+__device__ __forceinline__ void ssim_tile_col_pass(const gs_v2f (*s_h)[TH][TS], int ly, int lx, gs_v2f (&out)[N]) {
+#pragma unroll
+  for (int m = 0; m < N; ++m) out[m] = gs_v2f{0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 11; ++k) {
+    const gs_v2f w = {gw(k), gw(k)};
+#pragma unroll
+    for (int m = 0; m < N; ++m) out[m] = gs_fma2(w, s_h[m][ly + k][lx], out[m]);
+  }
 }
 
 __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
@@ -66,76 +170,30 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float* __r
   const int ox = blockIdx.x * TSX, oy = blockIdx.y * TS;
   const float* p1 = img1 + (size_t)plane * H * W;
   const float* p2 = img2 + (size_t)plane * H * W;
-  // Staging: every load goes to a clamped (always valid) address and is issued before the first LDS write, so a thread
-  // waits for HBM/L2 once — as a loop of predicated loads this was ten dependent round trips per thread and most of the
-  // kernel's duration.
-  {
-    float vx[STAGE_ITERS], vy[STAGE_ITERS];
-#pragma unroll
-    for (int j = 0; j < STAGE_ITERS; ++j) {
-      const int i = tid + 256 * j, r = i / SXP, c = i - r * SXP;
-      const size_t o = (size_t)min(max(oy + r - HALO, 0), H - 1) * W + min(max(ox + c - HALO, 0), W - 1);
-      vx[j] = p1[o]; vy[j] = p2[o];
-    }
-#pragma unroll
-    for (int j = 0; j < STAGE_ITERS; ++j) {
-      const int i = tid + 256 * j, r = i / SXP, c = i - r * SXP;
-      const int gy = oy + r - HALO, gx = ox + c - HALO;
-      const bool in = c < THX && gy >= 0 && gy < H && gx >= 0 && gx < W;
-      if (i < TH * SXP) { s_x[r][c] = in ? vx[j] : 0.f; s_y[r][c] = in ? vy[j] : 0.f; }
-    }
-  }
+  ssim_tile_stage<2>(tid, H, W, ox, oy, {p1, p2}, {s_x, s_y});
   __syncthreads();
-  for (int i = tid; i < ROW_ITEMS; i += 256) {
-    const int r = i >> 4, c = i & 15;
-    gs_v2f sx = {0.f, 0.f}, sy = sx, sxx = sx, syy = sx, sxy = sx;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const gs_v2f w = {gw(k), gw(k)};
-      const gs_v2f x = {s_x[r][c + k], s_x[r][c + TS + k]}, y = {s_y[r][c + k], s_y[r][c + TS + k]};
-      const gs_v2f wx = w * x, wy = w * y;
-      sx = gs_fma2(w, x, sx); sy = gs_fma2(w, y, sy);
-      sxx = gs_fma2(wx, x, sxx); syy = gs_fma2(wy, y, syy); sxy = gs_fma2(wx, y, sxy);
-    }
-    s_h[0][r][c] = sx; s_h[1][r][c] = sy; s_h[2][r][c] = sxx; s_h[3][r][c] = syy; s_h[4][r][c] = sxy;
-  }
+  ssim_tile_row_pass(tid, s_x, s_y, s_h);
   __syncthreads();
   const int ly = threadIdx.y, lx = threadIdx.x;
   float val = 0.f, l1 = 0.f;
   {
-    gs_v2f mu1 = {0.f, 0.f}, mu2 = mu1, exx = mu1, eyy = mu1, exy = mu1;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const gs_v2f w = {gw(k), gw(k)};
-      mu1 = gs_fma2(w, s_h[0][ly + k][lx], mu1); mu2 = gs_fma2(w, s_h[1][ly + k][lx], mu2);
-      exx = gs_fma2(w, s_h[2][ly + k][lx], exx); eyy = gs_fma2(w, s_h[3][ly + k][lx], eyy);
-      exy = gs_fma2(w, s_h[4][ly + k][lx], exy);
-    }
-    const gs_v2f two = {2.f, 2.f}, c1 = {C1, C1}, c2 = {C2, C2};
-    const gs_v2f mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-    const gs_v2f s1 = exx - mu1_sq, s2 = eyy - mu2_sq, s12 = exy - mu12;
-    const gs_v2f A = mu1_sq + mu2_sq + c1, B = s1 + s2 + c2, Cc = two * mu12 + c1, Dd = two * s12 + c2;
-    // two reciprocals per pixel (v_rcp_f32 + one Newton step: <= 1 ulp) instead of four IEEE divisions (~10 VALU ops each)
-    const gs_v2f invA = {ssim_rcp(A[0]), ssim_rcp(A[1])}, invB = {ssim_rcp(B[0]), ssim_rcp(B[1])};
-    const gs_v2f invAB = invA * invB;
-    const gs_v2f m = Cc * Dd * invAB;
-    const gs_v2f t = mu1 * two * Cc * Dd * invAB;
-    const gs_v2f d1 = (mu2 * two * Dd) * invAB - (mu2 * two * Cc) * invAB - t * invA + t * invB;
-    const gs_v2f d2 = -m * invB;
-    const gs_v2f d3 = two * Cc * invAB;
+    gs_v2f mo[5];
+    ssim_tile_col_pass(s_h, ly, lx, mo);
+    const SsimWindow<gs_v2f> pair = ssim_window(mo[0], mo[1], mo[2], mo[3], mo[4]);
     const int gy = oy + ly;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const int gx = ox + lx + half * TS;
       if (gx < W && gy < H) {
         const bool counted = gx >= crop && gx < W - crop && gy >= crop && gy < H - crop;
-        const bool same = ssim_equal_window(mu1[half], mu2[half], exx[half], eyy[half], exy[half]);
-        val += counted ? (same ? 1.f : m[half]) : 0.f;
+        const bool same = ssim_equal_window(mo[0][half], mo[1][half], mo[2][half], mo[3][half], mo[4][half], false);
+        const SsimWindow<float> win = ssim_exact(pair, half, same);
+        val += counted ? win.m : 0.f;
         const size_t o = (size_t)plane * H * W + (size_t)gy * W + gx;
         if (dm_dmu1) {
-          dm_dmu1[o] = counted ? (same ? 0.f : d1[half]) : 0.f;
-          dm_dsigma1_sq[o] = counted ? (same ? -invB[half] : d2[half]) : 0.f;
-          dm_dsigma12[o] = counted ? (same ? 2.f * invB[half] : d3[half]) : 0.f;
+          dm_dmu1[o] = counted ? win.d1 : 0.f;
+          dm_dsigma1_sq[o] = counted ? win.d2 : 0.f;
+          dm_dsigma12[o] = counted ? win.d3 : 0.f;
         }
         l1 += fabsf(s_x[ly + HALO][lx + half * TS + HALO] - s_y[ly + HALO][lx + half * TS + HALO]);
       }
@@ -153,24 +211,16 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float* __r
   }
 }
 
-// deterministic final reduction of the per-block partial sums (double accumulation)
+// the two means (and, if asked, the training loss) from the per-workgroup partial sums
 __global__ __launch_bounds__(1024) void k_ssim_finish(int nblocks, double inv_n, const float* __restrict__ partial,
                                                        float* __restrict__ ssim_mean, float* __restrict__ l1_mean,
                                                        float* __restrict__ loss, float lambda_dssim) {
-  __shared__ double s_a[16], s_b[16];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 1024) { a += (double)partial[2 * i]; b += (double)partial[2 * i + 1]; }
-  a = gs_wave_sum_row3_f64(a); b = gs_wave_sum_row3_f64(b);   // DPP adds; the totals are in lane 63
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 63) { s_a[wave] = a; s_b[wave] = b; }
-  __syncthreads();
+  float sm, lm;
+  gs_finish_two_means(nblocks, inv_n, partial, sm, lm);
   if (threadIdx.x == 0) {
-    double ta = 0.0, tb = 0.0;
-    for (int w = 0; w < 16; ++w) { ta += s_a[w]; tb += s_b[w]; }
-    const float sm = (float)(ta * inv_n), lm = (float)(tb * inv_n);
     if (ssim_mean) *ssim_mean = sm;
     if (l1_mean) *l1_mean = lm;
-    if (loss) *loss = (1.0f - lambda_dssim) * lm + lambda_dssim * (1.0f - sm);  // reference train.py:176
+    if (loss) *loss = gs_l1_ssim_loss(lambda_dssim, lm, sm);
   }
 }
 
@@ -182,7 +232,7 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(int H, int W, float inv_n, con
   __shared__ float s_a[TH][SXP];
   __shared__ float s_b[TH][SXP];
   __shared__ float s_c[TH][SXP];
-  __shared__ gs_v2f s_h[3][TH][TS];  // columns (c, c + 16) as one pair, see k_ssim_fwd
+  __shared__ gs_v2f s_h[3][TH][TS];  // row-pass results, columns (c, c + 16) as one pair
   const int tid = threadIdx.y * TS + threadIdx.x;
   const int plane = blockIdx.z;
   const int ox = blockIdx.x * TSX, oy = blockIdx.y * TS;
@@ -198,22 +248,7 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(int H, int W, float inv_n, con
     px[half] = img1[o]; py[half] = img2[o];
   }
   if (ks != 0.f) {
-    {  // staged with clamped addresses, all loads in flight before the first LDS write (see k_ssim_fwd)
-      float va[STAGE_ITERS], vb[STAGE_ITERS], vc[STAGE_ITERS];
-#pragma unroll
-      for (int j = 0; j < STAGE_ITERS; ++j) {
-        const int i = tid + 256 * j, r = i / SXP, c = i - r * SXP;
-        const size_t o = po + (size_t)min(max(oy + r - HALO, 0), H - 1) * W + min(max(ox + c - HALO, 0), W - 1);
-        va[j] = dm_dmu1[o]; vb[j] = dm_dsigma1_sq[o]; vc[j] = dm_dsigma12[o];
-      }
-#pragma unroll
-      for (int j = 0; j < STAGE_ITERS; ++j) {
-        const int i = tid + 256 * j, r = i / SXP, c = i - r * SXP;
-        const int gy = oy + r - HALO, gx = ox + c - HALO;
-        const bool in = c < THX && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        if (i < TH * SXP) { s_a[r][c] = in ? va[j] : 0.f; s_b[r][c] = in ? vb[j] : 0.f; s_c[r][c] = in ? vc[j] : 0.f; }
-      }
-    }
+    ssim_tile_stage<3>(tid, H, W, ox, oy, {dm_dmu1 + po, dm_dsigma1_sq + po, dm_dsigma12 + po}, {s_a, s_b, s_c});
     __syncthreads();
     for (int i = tid; i < ROW_ITEMS; i += 256) {
       const int r = i >> 4, c = i & 15;
@@ -232,14 +267,9 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(int H, int W, float inv_n, con
   const int ly = threadIdx.y, lx = threadIdx.x;
   const int gy = oy + ly;
   if (gy >= H) return;
-  gs_v2f a = {0.f, 0.f}, b = a, cc = a;
-  if (ks != 0.f) {
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const gs_v2f w = {gw(k), gw(k)};
-      a = gs_fma2(w, s_h[0][ly + k][lx], a); b = gs_fma2(w, s_h[1][ly + k][lx], b); cc = gs_fma2(w, s_h[2][ly + k][lx], cc);
-    }
-  }
+  gs_v2f abc[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+  if (ks != 0.f) ssim_tile_col_pass(s_h, ly, lx, abc);
+  const gs_v2f a = abc[0], b = abc[1], cc = abc[2];
 #pragma unroll
   for (int half = 0; half < 2; ++half) {
     const int gx = ox + lx + half * TS;
@@ -294,6 +324,18 @@ constexpr int FER = FT * FT / FTHREADS;   // output rows per thread in the last 
 constexpr int FCR = 7, FC_GROUPS = (FR1 + FCR - 1) / FCR;   // 6 groups x 42 columns = 252 items
 constexpr int FDR = 8, FD_GROUPS = FT / FDR;                // 4 groups x 42 rows = 168 items
 static_assert(FC_GROUPS * FR1 <= FTHREADS && FD_GROUPS * FR1 <= FTHREADS && FT % FDR == 0 && FDR % 2 == 0, "one item per thread");
+
+// the sliding 11-tap window over a register run: RUN + 10 inputs -> RUN consecutive outputs
+template <int RUN>
+__device__ __forceinline__ void ssim_run(const float (&v)[RUN + 10], float (&out)[RUN]) {
+#pragma unroll
+  for (int j = 0; j < RUN; ++j) {
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) a = fmaf(gw(k), v[j + k], a);
+    out[j] = a;
+  }
+}
 
 __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const float* __restrict__ img1, const float* __restrict__ img2,
                                                         float ks /* d loss / d ssim_mean / N */, float kl /* d loss / d l1_mean / N */,
@@ -379,34 +421,19 @@ __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const 
       float v[FCR + 10];
 #pragma unroll
       for (int t = 0; t < FCR + 10; ++t) v[t] = s_h[m][min(r0 + t, FR2 - 1)][c];   // (rows past the last one feed outputs that are not kept)
-#pragma unroll
-      for (int j = 0; j < FCR; ++j) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) a = fmaf(gw(k), v[j + k], a);
-        mo[m][j] = a;
-      }
+      ssim_run(v, mo[m]);
     }
     const int gx = ox + c - HALO;
 #pragma unroll
     for (int j = 0; j < FCR; ++j) {
       const int r = r0 + j, gy = oy + r - HALO;
-      const float mu1 = mo[0][j], mu2 = mo[1][j];
-      const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-      const float s1 = mo[2][j] - mu1_sq, s2 = mo[3][j] - mu2_sq, s12 = mo[4][j] - mu12;
-      const float A = mu1_sq + mu2_sq + C1, B = s1 + s2 + C2, Cc = 2.f * mu12 + C1, Dd = 2.f * s12 + C2;
-      const float invA = ssim_rcp(A), invB = ssim_rcp(B), invAB = invA * invB;
-      const float m = Cc * Dd * invAB;
-      const float t = mu1 * 2.f * Cc * Dd * invAB;
-      const float d1 = (mu2 * 2.f * Dd) * invAB - (mu2 * 2.f * Cc) * invAB - t * invA + t * invB;
-      const float d2 = -m * invB;
-      const float d3 = 2.f * Cc * invAB;
+      const SsimWindow<float> win = ssim_exact(ssim_window(mo[0][j], mo[1][j], mo[2][j], mo[3][j], mo[4][j]), 0,
+                                               ssim_equal_window(mo[0][j], mo[1][j], mo[2][j], mo[3][j], mo[4][j], false));
       const bool in_img = gx >= 0 && gx < W && gy >= 0 && gy < H && r < FR1;
-      const bool same = ssim_equal_window(mu1, mu2, mo[2][j], mo[3][j], mo[4][j]);
       // (the staged inputs stay readable until the barrier below: s_d aliases them, and phase C reads only s_h)
-      mo[0][j] = in_img ? (same ? 0.f : d1) : 0.f; mo[1][j] = in_img ? (same ? -invB : d2) : 0.f; mo[2][j] = in_img ? (same ? 2.f * invB : d3) : 0.f;
+      mo[0][j] = in_img ? win.d1 : 0.f; mo[1][j] = in_img ? win.d2 : 0.f; mo[2][j] = in_img ? win.d3 : 0.f;
       const bool in_tile = c >= HALO && c < HALO + FT && r >= HALO && r < HALO + FT;
-      val += (in_img && in_tile) ? (same ? 1.f : m) : 0.f;
+      val += (in_img && in_tile) ? win.m : 0.f;
     }
     // all phase-B readers of s_xy are past the barrier above, so the maps may overwrite it
 #pragma unroll
@@ -425,13 +452,10 @@ __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const 
         const float2 a = *reinterpret_cast<const float2*>(&s_d[m][r][c0 + t]);
         v[t] = a.x; v[t + 1] = a.y;
       }
+      float e[FDR];
+      ssim_run(v, e);
 #pragma unroll
-      for (int j = 0; j < FDR; ++j) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) a = fmaf(gw(k), v[j + k], a);
-        s_e[m][r][c0 + j] = a;   // s_e aliases s_h: every phase-C reader of s_h is past the barrier above
-      }
+      for (int j = 0; j < FDR; ++j) s_e[m][r][c0 + j] = e[j];   // s_e aliases s_h: every phase-C reader of s_h is past the barrier above
     }
   }
   __syncthreads();
@@ -444,13 +468,7 @@ __global__ __launch_bounds__(FTHREADS) void k_l1_ssim_fused(int H, int W, const 
       float v[FER + 10];
 #pragma unroll
       for (int t = 0; t < FER + 10; ++t) v[t] = s_e[m][er0 + t][ec];
-#pragma unroll
-      for (int j = 0; j < FER; ++j) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) a = fmaf(gw(k), v[j + k], a);
-        out[m][j] = a;
-      }
+      ssim_run(v, out[m]);
     }
     const int gx = ox + ec;
 #pragma unroll
@@ -538,23 +556,15 @@ struct GsLossProgram {
   float k[MI355GS_LOSS_PROGRAM_MAX];
 };
 
-// One launch: the two means finished from the pass's per-workgroup partial sums (the reduction of k_ssim_finish: double
-// accumulation, fixed order — the same bits), left in *ssim_mean / *l1_mean, then the recorded program evaluated on them.
+// One launch: the two means finished from the pass's per-workgroup partial sums, left in *ssim_mean / *l1_mean, then the
+// recorded program evaluated on them.
 __device__ __forceinline__ void loss_program_body(const GsLossProgram& p, int nblocks, double inv_n, const float* __restrict__ partial,
                                                   float* __restrict__ ssim_mean, float* __restrict__ l1_mean, float* __restrict__ out,
                                                   float* __restrict__ host_out, float ticket) {
 #pragma clang fp contract(off)   // one rounding per recorded operation, as eager PyTorch's elementwise kernels
-  __shared__ double s_a[16], s_b[16];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 1024) { a += (double)partial[2 * i]; b += (double)partial[2 * i + 1]; }
-  a = gs_wave_sum_row3_f64(a); b = gs_wave_sum_row3_f64(b);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 63) { s_a[wave] = a; s_b[wave] = b; }
-  __syncthreads();
+  float sm, lm;
+  gs_finish_two_means(nblocks, inv_n, partial, sm, lm);
   if (threadIdx.x != 0) return;
-  double ta = 0.0, tb = 0.0;
-  for (int w = 0; w < 16; ++w) { ta += s_a[w]; tb += s_b[w]; }
-  const float sm = (float)(ta * inv_n), lm = (float)(tb * inv_n);
   *ssim_mean = sm; *l1_mean = lm;
   float st[MI355GS_LOSS_PROGRAM_MAX];
   int sp = 0;
@@ -590,11 +600,15 @@ __global__ __launch_bounds__(1024) void k_loss_program(GsLossProgram p, int nblo
   loss_program_body(p, nblocks, inv_n, partial, ssim_mean, l1_mean, out, host_out, ticket);
 }
 
-// elements [i0, i0 + 4) of d_a = sl * sgn(a - b) + ss * dssim
+// elements [i0, i0 + 4) of d_a = sl * sgn(a - b) + ss * dssim, with sl = (gl * c_l1) / n and ss = gs * c_ssim from the incoming
+// gradients gl, gs
 __device__ __forceinline__ void loss_pair_bwd_four(long long n, long long i0, const float* __restrict__ a, const float* __restrict__ b,
-                                                   const float* __restrict__ dssim, float sl, float ss, bool use_l1, bool use_ss,
-                                                   float* __restrict__ d_a) {
+                                                   const float* __restrict__ dssim, float gl, float c_l1, float gs, float c_ssim,
+                                                   float n_as_float, float* __restrict__ d_a) {
 #pragma clang fp contract(off)
+  const float sl = (gl * c_l1) / n_as_float;
+  const float ss = gs * c_ssim;
+  const bool use_l1 = c_l1 != 0.0f, use_ss = c_ssim != 0.0f && dssim != nullptr;   // (a term that was never asked for adds no 0 * inf)
   auto one = [&](float x, float y, float ds) {
     const float d = x - y;
     const float tl = use_l1 ? (d > 0.f ? sl : (d < 0.f ? -sl : 0.f)) : 0.f;
@@ -615,10 +629,8 @@ __global__ __launch_bounds__(256) void k_loss_pair_bwd(long long n, const float*
                                                        const float* __restrict__ g_ssim, float c_ssim, float n_as_float,
                                                        float* __restrict__ d_a) {
 #pragma clang fp contract(off)
-  const float sl = ((g_l1 ? *g_l1 : 1.0f) * c_l1) / n_as_float;
-  const float ss = (g_ssim ? *g_ssim : 1.0f) * c_ssim;
-  const bool use_l1 = c_l1 != 0.0f, use_ss = c_ssim != 0.0f && dssim != nullptr;   // (a term that was never asked for adds no 0 * inf)
-  loss_pair_bwd_four(n, ((long long)blockIdx.x * 256 + threadIdx.x) * 4, a, b, dssim, sl, ss, use_l1, use_ss, d_a);
+  loss_pair_bwd_four(n, ((long long)blockIdx.x * 256 + threadIdx.x) * 4, a, b, dssim, g_l1 ? *g_l1 : 1.0f, c_l1, g_ssim ? *g_ssim : 1.0f, c_ssim,
+                     n_as_float, d_a);
 }
 
 // loss.backward() right behind the materialisation, i.e. with dL/d(value) = 1 known before anything is launched: ONE launch for
@@ -635,10 +647,7 @@ __global__ __launch_bounds__(1024) void k_loss_program_grad(GsLossProgram p, int
     loss_program_body(p, nblocks, inv_n, partial, ssim_mean, l1_mean, out, host_out, ticket);
     return;
   }
-  const float sl = (1.0f * c_l1) / n_as_float;
-  const float ss = 1.0f * c_ssim;
-  const bool use_l1 = c_l1 != 0.0f, use_ss = c_ssim != 0.0f && dssim != nullptr;
-  loss_pair_bwd_four(n, ((long long)(blockIdx.x - 1) * 1024 + threadIdx.x) * 4, a, b, dssim, sl, ss, use_l1, use_ss, d_a);
+  loss_pair_bwd_four(n, ((long long)(blockIdx.x - 1) * 1024 + threadIdx.x) * 4, a, b, dssim, 1.0f, c_l1, 1.0f, c_ssim, n_as_float, d_a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -651,7 +660,7 @@ __global__ __launch_bounds__(1024) void k_loss_program_grad(GsLossProgram p, int
 // per staged row and frame) is read ONCE from the interleaved bytes, converted through a 256-entry table of correctly rounded
 // quotients b / 255 (one IEEE division per thread; b * (1/255) differs in the last bit for 126 of the 256 values) and de-interleaved
 // into three float planes per frame in LDS; the squared byte differences of the tile's own pixels are summed on the way, in
-// integers.  The two window passes of k_ssim_fwd then run once per channel over those planes.
+// integers.  The two window passes of the 32x16 tile then run once per channel over those planes.
 // Loads: the rows of a W x 3 byte image start at any byte, and so may the frames (a slice of a stack of odd-sized frames).  With
 // W a multiple of 4 and both bases 4-byte aligned — uniform over the launch, decided on the host — every row and every tile's first
 // byte (96 bytes per tile column) is 4-byte aligned, and a staged row is the 32 words from 16 bytes before the tile's first byte;
@@ -661,34 +670,6 @@ constexpr int MB_ROW_WORDS = 32;                               // aligned path: 
 constexpr int MB_BYTE_ITERS = (TH * MB_ROW_BYTES + 255) / 256;  // 13
 constexpr int MB_WORD_ITERS = (TH * MB_ROW_WORDS + 255) / 256;  // 4
 static_assert(MB_ROW_WORDS * 4 >= MB_ROW_BYTES + 1 && (TSX * 3) % 4 == 0, "a staged row fits the aligned words");
-
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ uint32_t mb_dpp_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);   // lanes without a source read 0
-}
-// integer forms of gs_wave_sum_row3 / gs_wave_sum_row3_f64: the total lands in lanes 48..63
-__device__ __forceinline__ uint32_t mb_wave_sum_row3_u32(uint32_t v) {
-  v += mb_dpp_u32<0xB1>(v);
-  v += mb_dpp_u32<0x4E>(v);
-  v += mb_dpp_u32<0x141>(v);
-  v += mb_dpp_u32<0x140>(v);
-  v += mb_dpp_u32<0x142, 0xA>(v);
-  v += mb_dpp_u32<0x143, 0xC>(v);
-  return v;
-}
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ unsigned long long mb_dpp_u64(unsigned long long v) {
-  return ((unsigned long long)mb_dpp_u32<CTRL, ROW_MASK>((uint32_t)(v >> 32)) << 32) | mb_dpp_u32<CTRL, ROW_MASK>((uint32_t)v);
-}
-__device__ __forceinline__ unsigned long long mb_wave_sum_row3_u64(unsigned long long v) {
-  v += mb_dpp_u64<0xB1>(v);
-  v += mb_dpp_u64<0x4E>(v);
-  v += mb_dpp_u64<0x141>(v);
-  v += mb_dpp_u64<0x140>(v);
-  v += mb_dpp_u64<0x142, 0xA>(v);
-  v += mb_dpp_u64<0x143, 0xC>(v);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void k_metrics_rgb8(int H, int W, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                                                       float* __restrict__ part_ssim, uint32_t* __restrict__ part_sq, int aligned) {
@@ -707,7 +688,7 @@ __global__ __launch_bounds__(256) void k_metrics_rgb8(int H, int W, const uint8_
   s_lut[tid] = (float)tid / 255.0f;   // torch's div: the correctly rounded quotient
   uint32_t sq = 0;
   // Staging: every load goes to a clamped (always valid) address and is issued before the barrier that publishes the table, so a
-  // thread waits for HBM/L2 once (see k_ssim_fwd); what lies outside the image is staged as 0 ("same" padding with zeros).
+  // thread waits for HBM/L2 once (as ssim_tile_stage); what lies outside the image is staged as 0 ("same" padding with zeros).
   if (aligned) {
     uint32_t va[MB_WORD_ITERS], vb[MB_WORD_ITERS];
 #pragma unroll
@@ -763,45 +744,26 @@ __global__ __launch_bounds__(256) void k_metrics_rgb8(int H, int W, const uint8_
   float val = 0.f;
   for (int ch = 0; ch < 3; ++ch) {
     if (ch) __syncthreads();   // the column pass of the channel before has read s_h
-    for (int i = tid; i < ROW_ITEMS; i += 256) {
-      const int r = i >> 4, c = i & 15;
-      gs_v2f sx = {0.f, 0.f}, sy = sx, sxx = sx, syy = sx, sxy = sx;
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        const gs_v2f w = {gw(k), gw(k)};
-        const gs_v2f x = {s_x[ch][r][c + k], s_x[ch][r][c + TS + k]}, y = {s_y[ch][r][c + k], s_y[ch][r][c + TS + k]};
-        const gs_v2f wx = w * x, wy = w * y;
-        sx = gs_fma2(w, x, sx); sy = gs_fma2(w, y, sy);
-        sxx = gs_fma2(wx, x, sxx); syy = gs_fma2(wy, y, syy); sxy = gs_fma2(wx, y, sxy);
-      }
-      s_h[0][r][c] = sx; s_h[1][r][c] = sy; s_h[2][r][c] = sxx; s_h[3][r][c] = syy; s_h[4][r][c] = sxy;
-    }
+    ssim_tile_row_pass(tid, s_x[ch], s_y[ch], s_h);
     __syncthreads();
-    gs_v2f mu1 = {0.f, 0.f}, mu2 = mu1, exx = mu1, eyy = mu1, exy = mu1;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const gs_v2f w = {gw(k), gw(k)};
-      mu1 = gs_fma2(w, s_h[0][ly + k][lx], mu1); mu2 = gs_fma2(w, s_h[1][ly + k][lx], mu2);
-      exx = gs_fma2(w, s_h[2][ly + k][lx], exx); eyy = gs_fma2(w, s_h[3][ly + k][lx], eyy);
-      exy = gs_fma2(w, s_h[4][ly + k][lx], exy);
-    }
+    gs_v2f mo[5];
+    ssim_tile_col_pass(s_h, ly, lx, mo);
+    // The value half of ssim_window, written out: through the helper the compiler no longer sinks the equal-window test into the
+    // in-image branch and schedules the three channels into 140 VGPRs (three waves per SIMD) instead of 106.
+    const gs_v2f mu1 = mo[0], mu2 = mo[1], exx = mo[2], eyy = mo[3], exy = mo[4];
     const gs_v2f two = {2.f, 2.f}, c1 = {C1, C1}, c2 = {C2, C2};
     const gs_v2f mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
     const gs_v2f s1 = exx - mu1_sq, s2 = eyy - mu2_sq, s12 = exy - mu12;
-    const gs_v2f A = mu1_sq + mu2_sq + c1, B = s1 + s2 + c2, Cc = two * mu12 + c1, Dd = two * s12 + c2;
-    const gs_v2f invA = {ssim_rcp(A[0]), ssim_rcp(A[1])}, invB = {ssim_rcp(B[0]), ssim_rcp(B[1])};
-    const gs_v2f m = Cc * Dd * (invA * invB);
+    const gs_v2f A = ssim_sum_sq(mu1_sq, mu2, mu2_sq) + c1, B = s1 + s2 + c2, Cc = two * mu12 + c1, Dd = two * s12 + c2;
+    const gs_v2f m = Cc * Dd * (ssim_rcp(A) * ssim_rcp(B));
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      // A window whose five moments are bit-equal for the two frames has SSIM exactly 1 (A = C and B = D); the formula gets there
-      // only to the reciprocals' ulp.  Nothing is differentiated here, so the all-zero window takes the exact value too (cf.
-      // ssim_equal_window): a pair of identical frames, black ones included, scores 1.0f exactly.
-      const bool same = mu1[half] == mu2[half] && exx[half] == eyy[half] && exx[half] == exy[half];
+      const bool same = ssim_equal_window(mu1[half], mu2[half], exx[half], eyy[half], exy[half], true);   // zero windows too
       if (ox + lx + half * TS < W && gy < H) val += same ? 1.f : m[half];
     }
   }
   val = gs_wave_sum_row3(val);   // the totals are in lane 63
-  sq = mb_wave_sum_row3_u32(sq);  // at most 512 x 3 x 65025 per workgroup: 32 bits hold it
+  sq = gs_wave_sum_row3(sq);  // at most 512 x 3 x 65025 per workgroup: 32 bits hold it
   const int wave = tid >> 6, lane = tid & 63;
   if (lane == 63) { s_red[wave] = val; s_redu[wave] = sq; }
   __syncthreads();
@@ -812,7 +774,7 @@ __global__ __launch_bounds__(256) void k_metrics_rgb8(int H, int W, const uint8_
   }
 }
 
-// One workgroup per frame pair: its tiles' partial sums in a fixed order, the SSIM sum in double (as k_ssim_finish), the squared
+// One workgroup per frame pair: its tiles' partial sums in a fixed order, the SSIM sum in double, the squared
 // differences in 64-bit integers.
 __global__ __launch_bounds__(256) void k_metrics_rgb8_finish(int tiles, double n, const float* __restrict__ part_ssim,
                                                              const uint32_t* __restrict__ part_sq, int64_t* __restrict__ sq_sum,
@@ -823,7 +785,7 @@ __global__ __launch_bounds__(256) void k_metrics_rgb8_finish(int tiles, double n
   double acc = 0.0;
   unsigned long long q = 0;
   for (int i = threadIdx.x; i < tiles; i += 256) { acc += (double)part_ssim[base + i]; q += part_sq[base + i]; }
-  acc = gs_wave_sum_row3_f64(acc); q = mb_wave_sum_row3_u64(q);
+  acc = gs_wave_sum_row3(acc); q = gs_wave_sum_row3(q);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 63) { s_a[wave] = acc; s_q[wave] = q; }
   __syncthreads();
@@ -838,6 +800,34 @@ __global__ __launch_bounds__(256) void k_metrics_rgb8_finish(int tiles, double n
 static inline int l1_nblocks(long long n) { return (int)((n + L1_THREADS * L1_PER_THREAD - 1) / (L1_THREADS * L1_PER_THREAD)); }
 
 static inline int ssim_nblocks(int B, int C, int H, int W) { return B * C * ((H + TS - 1) / TS) * ((W + TSX - 1) / TSX); }
+static inline int fused_nblocks(int B, int C, int H, int W) { return B * C * ((H + FT - 1) / FT) * ((W + FT - 1) / FT); }
+
+// The kernels that take tw x th tiles of (batch, channel) planes: the sizes that can be launched (the planes are the grid's z
+// dimension) and the grid.
+static inline bool planes_ok(int B, int C, int H, int W) { return B > 0 && C > 0 && H > 0 && W > 0 && (size_t)B * C <= 65535; }
+static inline dim3 plane_grid(int planes, int H, int W, int tw, int th) { return dim3((W + tw - 1) / tw, (H + th - 1) / th, planes); }
+
+// k_l1_ssim_fused over `planes` planes: dL_dimg1 = ks * d(ssim sum)/dimg1 + kl * d(l1 sum)/dimg1, both sums' per-workgroup partials
+// in `scratch`.  `name`: the launch's range in a marker trace.
+static int launch_l1_ssim_fused(hipStream_t stream, int planes, int H, int W, const float* img1, const float* img2, float ks, float kl,
+                                float* dL_dimg1, void* scratch, const char* name) {
+  const int debug = 0;
+  {
+    GsProfScope prof(3, stream);
+    GS_KRANGE(name);
+    hipLaunchKernelGGL(k_l1_ssim_fused, plane_grid(planes, H, W, FT, FT), dim3(FTHREADS), 0, stream, H, W, img1, img2, ks, kl, dL_dimg1,
+                       (float*)scratch);
+  }
+  GS_CHECK_LAUNCH(name);
+  return MI355GS_OK;
+}
+// ... for loss = (1-l) * L1 + l * (1 - SSIM) with d loss = 1
+static int launch_l1_ssim_loss(hipStream_t stream, int planes, int H, int W, const float* img1, const float* img2, float lambda_dssim,
+                               float* dL_dimg1, void* scratch) {
+  const double inv_n = 1.0 / ((double)planes * H * W);
+  return launch_l1_ssim_fused(stream, planes, H, W, img1, img2, (float)(-(double)lambda_dssim * inv_n),
+                              (float)((1.0 - (double)lambda_dssim) * inv_n), dL_dimg1, scratch, "l1_ssim_fused");
+}
 
 extern "C" {
 
@@ -851,14 +841,13 @@ int mi355gs_ssim_forward(void* stream_, int B, int C, int H, int W, const float*
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
   const int debug = 0;
-  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !scratch) return MI355GS_EINVAL;
+  if (!planes_ok(B, C, H, W) || !img1 || !img2 || !scratch) return MI355GS_EINVAL;
   const int crop = padding_valid ? HALO : 0;
   if (padding_valid && (l1_mean || H <= 2 * HALO || W <= 2 * HALO)) return MI355GS_EINVAL;
   if ((dm_dmu1 == nullptr) != (dm_dsigma1_sq == nullptr) || (dm_dmu1 == nullptr) != (dm_dsigma12 == nullptr)) return MI355GS_EINVAL;
-  if ((size_t)B * C > 65535) return MI355GS_EINVAL;
-  const dim3 grid((W + TSX - 1) / TSX, (H + TS - 1) / TS, B * C);
   GS_KRANGE("ssim_fwd");
-  hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(TS, TS), 0, stream, H, W, img1, img2, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, (float*)scratch, crop);
+  hipLaunchKernelGGL(k_ssim_fwd, plane_grid(B * C, H, W, TSX, TS), dim3(TS, TS), 0, stream, H, W, img1, img2, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
+                     (float*)scratch, crop);
   GS_CHECK_LAUNCH("ssim_fwd");
   // one finishing launch normalises both sums by the same count: with "valid" padding that is the cropped map's, so the L1
   // mean (a "same"-padding quantity of the training loss) is only offered with padding_valid == 0
@@ -876,17 +865,15 @@ int mi355gs_ssim_backward(void* stream_, int B, int C, int H, int W, const float
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
   const int debug = 0;
-  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !dL_dimg1) return MI355GS_EINVAL;
+  if (!planes_ok(B, C, H, W) || !img1 || !img2 || !dL_dimg1) return MI355GS_EINVAL;
   if (ssim_grad_scale && (!dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12)) return MI355GS_EINVAL;
-  if ((size_t)B * C > 65535) return MI355GS_EINVAL;
-  const dim3 grid((W + TSX - 1) / TSX, (H + TS - 1) / TS, B * C);
   const int crop = padding_valid ? HALO : 0;
   if (padding_valid && (l1_grad_scale || H <= 2 * HALO || W <= 2 * HALO)) return MI355GS_EINVAL;
   // the forward zeroed the saved partials outside the counted region, so the same kernel serves both paddings
   const float inv_n = (float)(1.0 / ((double)B * C * (H - 2 * crop) * (W - 2 * crop)));
   GS_KRANGE("ssim_bwd");
-  hipLaunchKernelGGL(k_ssim_bwd, grid, dim3(TS, TS), 0, stream, H, W, inv_n, img1, img2, dm_dmu1, dm_dsigma1_sq, dm_dsigma12,
-                     ssim_grad_scale, l1_grad_scale, ssim_grad_scale ? 1.f : 0.f, l1_grad_scale ? 1.f : 0.f, dL_dimg1);
+  hipLaunchKernelGGL(k_ssim_bwd, plane_grid(B * C, H, W, TSX, TS), dim3(TS, TS), 0, stream, H, W, inv_n, img1, img2, dm_dmu1, dm_dsigma1_sq,
+                     dm_dsigma12, ssim_grad_scale, l1_grad_scale, ssim_grad_scale ? 1.f : 0.f, l1_grad_scale ? 1.f : 0.f, dL_dimg1);
   GS_CHECK_LAUNCH("ssim_bwd");
   return MI355GS_OK;
 }
@@ -919,8 +906,6 @@ int mi355gs_l1_loss_backward(void* stream_, int64_t n, const float* a, const flo
   return MI355GS_OK;
 }
 
-static inline int fused_nblocks(int B, int C, int H, int W) { return B * C * ((H + FT - 1) / FT) * ((W + FT - 1) / FT); }
-
 // loss = (1-l) * L1 + l * (1 - SSIM) AND dloss/dimg1 from one pass over the images (k_l1_ssim_fused): the binding's forward keeps
 // the gradient and its backward only scales it by the incoming dL/dloss.
 int mi355gs_l1_ssim_loss_fused(void* stream_, int B, int C, int H, int W, const float* img1, const float* img2, void* scratch,
@@ -928,17 +913,10 @@ int mi355gs_l1_ssim_loss_fused(void* stream_, int B, int C, int H, int W, const 
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
   const int debug = 0;
-  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !scratch || !loss || !dloss_dimg1) return MI355GS_EINVAL;
-  if ((size_t)B * C > 65535) return MI355GS_EINVAL;
+  if (!planes_ok(B, C, H, W) || !img1 || !img2 || !scratch || !loss || !dloss_dimg1) return MI355GS_EINVAL;
+  const int rc = launch_l1_ssim_loss(stream, B * C, H, W, img1, img2, lambda_dssim, dloss_dimg1, scratch);
+  if (rc != MI355GS_OK) return rc;
   const double inv_n = 1.0 / ((double)B * C * H * W);
-  const dim3 grid((W + FT - 1) / FT, (H + FT - 1) / FT, B * C);
-  {
-    GsProfScope prof(3, stream);
-    GS_KRANGE("l1_ssim_fused");
-    hipLaunchKernelGGL(k_l1_ssim_fused, grid, dim3(FTHREADS), 0, stream, H, W, img1, img2, (float)(-(double)lambda_dssim * inv_n),
-                       (float)((1.0 - (double)lambda_dssim) * inv_n), dloss_dimg1, (float*)scratch);
-  }
-  GS_CHECK_LAUNCH("l1_ssim_fused");
   GS_KRANGE("ssim_finish");
   hipLaunchKernelGGL(k_ssim_finish, dim3(1), dim3(1024), 0, stream, fused_nblocks(B, C, H, W), inv_n, (const float*)scratch, ssim_mean,
                      l1_mean, loss, lambda_dssim);
@@ -949,19 +927,9 @@ int mi355gs_l1_ssim_loss_fused(void* stream_, int B, int C, int H, int W, const 
 int mi355gs_l1_ssim_pair_forward(void* stream_, int B, int C, int H, int W, const float* img1, const float* img2, void* scratch,
                                  float* dssim_dimg1) {
   GS_RANGE();
-  hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
-  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || !img1 || !img2 || !scratch || !dssim_dimg1) return MI355GS_EINVAL;
-  if ((size_t)B * C > 65535) return MI355GS_EINVAL;
-  const double inv_n = 1.0 / ((double)B * C * H * W);
-  const dim3 grid((W + FT - 1) / FT, (H + FT - 1) / FT, B * C);
-  {
-    GsProfScope prof(3, stream);
-    GS_KRANGE("l1_ssim_pair");
-    hipLaunchKernelGGL(k_l1_ssim_fused, grid, dim3(FTHREADS), 0, stream, H, W, img1, img2, (float)inv_n, 0.0f, dssim_dimg1, (float*)scratch);
-  }
-  GS_CHECK_LAUNCH("l1_ssim_pair");
-  return MI355GS_OK;
+  if (!planes_ok(B, C, H, W) || !img1 || !img2 || !scratch || !dssim_dimg1) return MI355GS_EINVAL;
+  return launch_l1_ssim_fused((hipStream_t)stream_, B * C, H, W, img1, img2, (float)(1.0 / ((double)B * C * H * W)), 0.0f, dssim_dimg1, scratch,
+                              "l1_ssim_pair");
 }
 
 int mi355gs_l1_ssim_pair_backward(void* stream_, int64_t n, const float* img1, const float* img2, const float* dssim_dimg1,
@@ -1053,9 +1021,8 @@ int mi355gs_metrics_rgb8(void* stream_, int N, int H, int W, const uint8_t* a, c
   float* part_ssim = (float*)scratch;
   uint32_t* part_sq = (uint32_t*)((char*)scratch + gs_align((size_t)N * tiles * sizeof(float)));
   const int aligned = (W % 4 == 0) && ((((uintptr_t)a | (uintptr_t)b) & 3) == 0);
-  const dim3 grid((W + TSX - 1) / TSX, (H + TS - 1) / TS, N);
   GS_KRANGE("metrics_rgb8");
-  hipLaunchKernelGGL(k_metrics_rgb8, grid, dim3(TS, TS), 0, stream, H, W, a, b, part_ssim, part_sq, aligned);
+  hipLaunchKernelGGL(k_metrics_rgb8, plane_grid(N, H, W, TSX, TS), dim3(TS, TS), 0, stream, H, W, a, b, part_ssim, part_sq, aligned);
   GS_CHECK_LAUNCH("metrics_rgb8");
   GS_KRANGE("metrics_rgb8_finish");
   hipLaunchKernelGGL(k_metrics_rgb8_finish, dim3(N), dim3(256), 0, stream, tiles, 3.0 * (double)H * (double)W, (const float*)part_ssim,
@@ -1070,16 +1037,6 @@ int mi355gs_metrics_rgb8(void* stream_, int N, int H, int W, const uint8_t* a, c
 // (gs_loss_partials_info) by a kernel the step runs anyway
 int gs_loss_fused(hipStream_t stream, int C, int H, int W, const float* img1, const float* img2, float lambda_dssim, float* dL_dimg1,
                   void* scratch) {
-  const int debug = 0;
-  const double inv_n = 1.0 / ((double)C * H * W);
-  const dim3 grid((W + FT - 1) / FT, (H + FT - 1) / FT, C);
-  {
-    GsProfScope prof(3, stream);
-    GS_KRANGE("l1_ssim_fused");
-    hipLaunchKernelGGL(k_l1_ssim_fused, grid, dim3(FTHREADS), 0, stream, H, W, img1, img2, (float)(-(double)lambda_dssim * inv_n),
-                       (float)((1.0 - (double)lambda_dssim) * inv_n), dL_dimg1, (float*)scratch);
-  }
-  GS_CHECK_LAUNCH("l1_ssim_fused");
-  return MI355GS_OK;
+  return launch_l1_ssim_loss(stream, C, H, W, img1, img2, lambda_dssim, dL_dimg1, scratch);
 }
 int gs_loss_fused_nblocks(int C, int H, int W) { return fused_nblocks(1, C, H, W); }
