@@ -518,6 +518,43 @@ size_t mi355gs_metrics_rgb8_scratch_bytes(int N, int H, int W);
 int mi355gs_metrics_rgb8(void* stream, int N, int H, int W, const uint8_t* a, const uint8_t* b, void* scratch, int64_t* sq_sum,
                          float* ssim_mean);
 
+/* ----------------------------------------------------------------------------------------------
+ * The tail of the init stage (reference init_geo.py:61-129 behind `compute_global_alignment`; utils/sfm_utils.py:250-432):
+ * confidence statistics, co-visibility masks and the ordered compaction of V aligned pointmaps.  All arrays are device memory,
+ * contiguous: pointmaps float [V][H][W][3], depthmaps / confidences float [V][H][W], images float [V][H][W][3] in [0,1],
+ * intrinsics float [V][3][3], w2c float [V][4][4] (row-major), overlap uint8 [V][H][W] (a torch.bool tensor's memory; 1 =
+ * co-visible, redundant).  Every call enqueues on the caller's stream; no allocation, no memset, no host synchronisation, no
+ * atomics (results are the same bits run to run).  Limits (MI355GS_EINVAL beyond them, as for null pointers and non-positive
+ * sizes; the scratch-size queries then return 0): V <= 256, V H W <= 2^31 - 1.
+ *
+ *   pointmap_stats (2 launches): stats[v] = (min of depthmaps[v], max of depthmaps[v], sum of confidences[v]) as three doubles —
+ *     min and max are the float32 values (a NaN propagates, as numpy's), the sum is accumulated in double in a fixed order.  The
+ *     pass also CLEARS overlap: the masks need no memset.  scratch: mi355gs_pointmap_stats_scratch_bytes() bytes.
+ *   covis_masks (1 launch over all V (V - 1) / 2 pairs; none for V == 1): `compute_co_vis_masks` (utils/sfm_utils.py:375-415).
+ *     order: HOST array of V ints, a permutation of 0 .. V-1 (the confidence ranking, or 0 .. V-1).  For the view c of rank i and
+ *     every point of the views of rank j < i: projection in double from the float32 inputs (cam = E [p,1], h = K cam, x = h0 / h2,
+ *     y = h1 / h2), valid when 0 <= x < W and 0 <= y < H on the doubles, pixel = truncation; the point's depth in its own view,
+ *     normalised in float32 with the min / max over all views ranked before c, against c's depth at the pixel normalised with c's
+ *     own min / max; |difference| < depth_threshold (float32) stores 1 into overlap[c][y][x].  stats: what pointmap_stats wrote
+ *     for these depthmaps; overlap: cleared by that call (or by the caller).  The first-ranked view is never marked.
+ *   compact_pointmaps (3 launches: count per block of 1024 elements, a one-workgroup scan that loops over any number of block
+ *     counts, ordered scatter): over the n = V H W elements in memory order, those with overlap == 0 (overlap null: all) go to
+ *     out_points [M][3], out_rgb8 [M][3] ((uint8)(clamp(image, 0, 1) * 255.f): one float32 multiply, truncation — what
+ *     `save_points3D` and storePly's uint8 fields make of the colours) and out_confidence [M][1], in the same order.  The out
+ *     arrays must hold n rows.  M goes to *count_dev (device int32) and, when count_host is non-null, to that word too: host
+ *     memory the device can write (pinned, mapped), read by the host once the stream has passed the call.
+ *     scratch: mi355gs_compact_scratch_bytes(n) bytes.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_pointmap_stats_scratch_bytes(int V, int H, int W);
+int mi355gs_pointmap_stats(void* stream, int V, int H, int W, const float* depthmaps, const float* confidences, uint8_t* overlap,
+                           void* scratch, double* stats);
+int mi355gs_covis_masks(void* stream, int V, int H, int W, const int32_t* order, const float* pointmaps, const float* depthmaps,
+                        const float* intrinsics, const float* w2c, const double* stats, float depth_threshold, uint8_t* overlap);
+size_t mi355gs_compact_scratch_bytes(int64_t n);
+int mi355gs_compact_pointmaps(void* stream, int64_t n, const uint8_t* overlap, const float* pointmaps, const float* images,
+                              const float* confidences, void* scratch, float* out_points, uint8_t* out_rgb8, float* out_confidence,
+                              int32_t* count_dev, int32_t* count_host);
+
 #ifdef __cplusplus
 }
 #endif

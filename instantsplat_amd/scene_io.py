@@ -130,7 +130,8 @@ def read_colmap_cameras(extrinsics: dict, intrinsics: dict, images_folder: str):
     return infos, poses
 
 
-def read_colmap_scene_info(path: str, images: Optional[str], eval: bool, n_views: int) -> SceneInfo:
+def read_colmap_scene_info(path: str, images: Optional[str], eval: bool, n_views: int, read_points: bool = True) -> SceneInfo:
+    """read_points=False: points3D.ply is not read (points / colors / normals are None): the caller has the cloud already."""
     sub = "1" if eval else "0"
     extr = iof.read_images_text(os.path.join(path, f"sparse_{n_views}/{sub}", "images.txt"))
     intr = iof.read_cameras_text(os.path.join(path, f"sparse_{n_views}/{sub}", "cameras.txt"))
@@ -139,10 +140,12 @@ def read_colmap_scene_info(path: str, images: Optional[str], eval: bool, n_views
     cam_infos = [unsorted_infos[i] for i in order]
     sorted_poses = [poses[i] for i in order]
     ply_path = os.path.join(path, f"sparse_{n_views}/0/points3D.ply")   # (also under --eval: the points live in /0)
-    v = iof.read_ply_vertices(ply_path)
-    points = np.vstack([v["x"], v["y"], v["z"]]).T
-    colors = np.vstack([v["red"], v["green"], v["blue"]]).T / 255.0
-    normals = np.vstack([v["nx"], v["ny"], v["nz"]]).T
+    points = colors = normals = None
+    if read_points:
+        v = iof.read_ply_vertices(ply_path)
+        points = np.vstack([v["x"], v["y"], v["z"]]).T
+        colors = np.vstack([v["red"], v["green"], v["blue"]]).T / 255.0
+        normals = np.vstack([v["nx"], v["ny"], v["nz"]]).T
     return SceneInfo(points=points, colors=colors, normals=normals, train_cameras=cam_infos, test_cameras=cam_infos if eval else [],
                      nerf_normalization=get_nerfpp_norm(cam_infos), ply_path=ply_path, train_poses=sorted_poses,
                      test_poses=sorted_poses if eval else [])
@@ -211,14 +214,17 @@ def load_confidence_lr(source_path: str, n_views: int, device, scale=(1.0, 100.0
 
 def load_init_scene(source_path: str, n_views: int, images: Optional[str] = None, eval: bool = False, resolution=1, shuffle: bool = True,
                     device="cuda", model_path: Optional[str] = None, init_scale_from_view_depth: bool = False,
-                    rng: Optional[random.Random] = None) -> InitScene:
+                    rng: Optional[random.Random] = None, pointcloud=None) -> InitScene:
     """Everything reference train.py:90-97 has in hand before `training_setup`, from the init directory.  `rng` stands for the
     reference's process-wide `random` module (seeded 0 by `safe_state`): the camera shuffle draws from it first, the training
-    loop's view sampling continues on the same stream (`InitScene.rng`)."""
+    loop's view sampling continues on the same stream (`InitScene.rng`).
+    pointcloud: (points [N,3], colors [N,3] in [0,1], confidence_lr [N,1] or None), tensors on any device, of a caller that
+    holds the cloud already (`init_stage.init_from_pointmaps`): they become the scene's as they are, and neither points3D.ply
+    nor confidence_dsp.npy is read.  Default None: both files are read."""
     rng = rng if rng is not None else random.Random(0)
     if not os.path.exists(os.path.join(source_path, f"sparse_{n_views}")):
         raise FileNotFoundError(f"Could not recognize scene type: {source_path}/sparse_{n_views} does not exist")
-    info = read_colmap_scene_info(source_path, images, eval, n_views)
+    info = read_colmap_scene_info(source_path, images, eval, n_views, read_points=pointcloud is None)
     if model_path:   # scene/__init__.py:52-65
         os.makedirs(model_path, exist_ok=True)
         shutil.copyfile(info.ply_path, os.path.join(model_path, "input.ply"))
@@ -242,12 +248,17 @@ def load_init_scene(source_path: str, n_views: int, images: Optional[str] = None
     test_cams = [load_cam(c, i, resolution, 1.0, device) for i, c in enumerate(test_infos)]
     scale_gaussian = None
     if init_scale_from_view_depth:
-        scale_gaussian = scale_from_view_depth(info.points, np.linalg.inv(info.train_poses),
+        host_points = info.points if pointcloud is None else pointcloud[0].detach().cpu().numpy()
+        scale_gaussian = scale_from_view_depth(host_points, np.linalg.inv(info.train_poses),
                                                [[fov2focal(c.FovX, c.width), fov2focal(c.FovY, c.height)] for c in train_infos])
+    if pointcloud is not None:
+        points, colors, confidence_lr = pointcloud
+    else:
+        points = torch.from_numpy(np.ascontiguousarray(info.points)).float()
+        colors = torch.from_numpy(np.ascontiguousarray(info.colors)).float()
+        confidence_lr = load_confidence_lr(source_path, n_views, device)
     return InitScene(source_path=source_path, n_views=n_views, cameras=cams, test_cameras=test_cams, cameras_extent=extent,
-                     points=torch.from_numpy(np.ascontiguousarray(info.points)).float(),
-                     colors=torch.from_numpy(np.ascontiguousarray(info.colors)).float(),
-                     confidence_lr=load_confidence_lr(source_path, n_views, device), scale_gaussian=scale_gaussian, info=info, rng=rng)
+                     points=points, colors=colors, confidence_lr=confidence_lr, scale_gaussian=scale_gaussian, info=info, rng=rng)
 
 
 def load_cameras(poses: np.ndarray, cameras: List[Camera]) -> List[Camera]:
@@ -290,30 +301,45 @@ def rotmat2qvec(R: np.ndarray) -> np.ndarray:
 
 
 def write_init_scene(source_path: str, w2c: List[np.ndarray], fovs, images: List[torch.Tensor], points: torch.Tensor, colors: torch.Tensor,
-                     confidence: Optional[torch.Tensor], names: Optional[List[str]] = None, subdir: str = "0") -> None:
+                     confidence: Optional[torch.Tensor], names: Optional[List[str]] = None, subdir: str = "0",
+                     n_views: Optional[int] = None, cameras=None) -> None:
     """The layout of Appendix F for V views: `w2c[v]` [4,4], `fovs[v]` = (FoVx, FoVy), `images[v]` float [3,H,W] in [0,1]
-    (stored as 8-bit PNG) or the path of an image file (copied under `names[v]`), points / colours [N,3], confidence [N,1] or None."""
+    (stored as 8-bit PNG) or the path of an image file (copied under `names[v]`), points / colours [N,3], confidence [N,1] or None.
+    n_views: the number in `sparse_<n>` when it is not the number of poses written (the test poses of sparse_<n>/1).
+    cameras: per view (width, height, fx, fy), written to cameras.txt as they are with the principal point at the centre (what
+    reference utils/sfm_utils.py:227-247 `save_intrinsics` writes); `fovs` is then not used, and `images[v]` may be None: no
+    image file is written for that view."""
     from PIL import Image
     V = len(w2c)
     names = names or [f"{v:04d}.png" for v in range(V)]
-    sparse = os.path.join(source_path, f"sparse_{V}", subdir)
+    sparse = os.path.join(source_path, f"sparse_{V if n_views is None else int(n_views)}", subdir)
     os.makedirs(sparse, exist_ok=True)
     os.makedirs(os.path.join(source_path, "images"), exist_ok=True)
     cams, imgs = {}, {}
     for v in range(V):
-        if isinstance(images[v], (str, os.PathLike)):   # an image FILE (a photograph, a video frame): copied as it is, decoded by the loader
-            with Image.open(images[v]) as im:
-                W, H = im.size
+        image = images[v] if images is not None else None
+        is_file = isinstance(image, (str, os.PathLike))   # an image FILE (a photograph, a video frame): copied as it is, decoded by the loader
+        if cameras is not None:
+            W, H, fx, fy = cameras[v]
         else:
-            H, W = int(images[v].shape[1]), int(images[v].shape[2])
+            if is_file:
+                with Image.open(image) as im:
+                    W, H = im.size
+            else:
+                H, W = int(image.shape[1]), int(image.shape[2])
+            fx, fy = fov2focal(fovs[v][0], W), fov2focal(fovs[v][1], H)
         m = np.asarray(w2c[v], dtype=np.float64)
-        cams[v + 1] = iof.ColmapCamera(v + 1, "PINHOLE", W, H, np.array([fov2focal(fovs[v][0], W), fov2focal(fovs[v][1], H), W / 2, H / 2]))
+        cams[v + 1] = iof.ColmapCamera(v + 1, "PINHOLE", int(W), int(H), np.array([fx, fy, W / 2, H / 2]))
         imgs[v + 1] = iof.ColmapImage(v + 1, rotmat2qvec(m[:3, :3]), m[:3, 3].copy(), v + 1, names[v])
-        if isinstance(images[v], (str, os.PathLike)):
-            shutil.copyfile(images[v], os.path.join(source_path, "images", names[v]))
+        if image is None:
             continue
-        arr = (images[v].detach().cpu().clamp(0, 1).permute(1, 2, 0).numpy() * 255.0).round().astype(np.uint8)
-        Image.fromarray(arr).save(os.path.join(source_path, "images", names[v]))
+        target = os.path.join(source_path, "images", names[v])
+        if is_file:
+            if os.path.abspath(image) != os.path.abspath(target):
+                shutil.copyfile(image, target)
+            continue
+        arr = (image.detach().cpu().clamp(0, 1).permute(1, 2, 0).numpy() * 255.0).round().astype(np.uint8)
+        Image.fromarray(arr).save(target)
     iof.write_cameras_text(os.path.join(sparse, "cameras.txt"), cams)
     iof.write_images_text(os.path.join(sparse, "images.txt"), imgs)
     if subdir == "0":
