@@ -555,6 +555,56 @@ int mi355gs_compact_pointmaps(void* stream, int64_t n, const uint8_t* overlap, c
                               const float* confidences, void* scratch, float* out_points, uint8_t* out_rgb8, float* out_confidence,
                               int32_t* count_dev, int32_t* count_host);
 
+/* ----------------------------------------------------------------------------------------------
+ * The global alignment loop (reference dust3r/cloud_opt/base_opt.py:326-366 `global_alignment_loop` over
+ * dust3r/cloud_opt/optimizer.py:188-201 `PointCloudOptimizer.forward`; run by init_geo.py:48 with 300 iterations and by
+ * init_test_pose.py:59 with 500): V images of H x W, E directed edges (i, j) that cover every image, n = H W.  Per iteration a
+ * log-depth map, a camera pose and a focal per image and a similarity transform per edge take one Adam step (betas 0.9 / 0.9,
+ * eps 1e-8) on
+ *   loss = (sum_e sum_p wi_e[p] |X_i[p] - M_e A_e[p]| + sum_e sum_p wj_e[p] |X_j[p] - M_e B_e[p]|) / (E n),   w = log(conf),
+ *   X_v[p] = R_v (d u / f, d v / f, d) + T_v with d = exp(depth_log), (u, v) = (col, row) - pp, f = exp(focal_log / 20),
+ *   pp = (W / 2, H / 2) + 10 pp_raw;  R = rotation of q / |q| (q scalar-last, x y z w), T = sign(t) expm1(|t|);
+ *   M_e = sigma_e [R_e | T_e], sigma_e = exp(s_e) exp(log(base_scale) - mean(s)) with MI355GS_ALIGN_NORM_PW_SCALE, else exp(s_e).
+ * The gradient of the norm at a zero residual is 0.  State, all device float, contiguous: depth_log [V][n], im_pose [V][7]
+ * (q, t), focal_log [V], pp_raw [V][2] (constant), pw_pose [E][8] (q, t, s); the Adam moments m_* / v_* have the shapes of their
+ * parameters.  Every call enqueues on the caller's stream.  A run makes 1 + 3 niter launches and nothing else: no allocation, no
+ * memset, no event, no host synchronisation, no float atomics — two runs from the same state give the same bits.  (The handle's
+ * FIRST call, whichever it is, also copies the edge-side tables to the device and waits for that copy.)
+ *
+ *   workspace_bytes / create / destroy: the handle pattern of the tracker.  edges: HOST array [E][2].  flags: MI355GS_ALIGN_*
+ *     below, the reference's requires_grad switches and norm_pw_scale (optimizer.py:66-91).  create returns null, and
+ *     workspace_bytes 0, for a null pointer, a non-positive size, an edge with i == j or an index outside [0, V), an image that
+ *     no edge covers, V > 256, E > 65535, E H W > 2^31 - 1 (or H W > 2^31 - 1025), flags outside the mask, base_scale <= 0.
+ *   pack: the handle's 16-byte records (x, y, z, log conf) from pred_i / pred_j [E][n][3] and conf_i / conf_j [E][n] (the
+ *     reference's _stacked_pred_i / _j and conf_i / conf_j, optimizer.py:50-57); once per problem, before grad / run.
+ *   grad: the loss and every gradient at the given state, nothing updated (tests; as mi355gs_trainer_grad).
+ *   run: niter iterations (base_opt.py:349-366).  step_table: device float [niter][4], row k = (-lr_k / (1 - 0.9^t),
+ *     sqrt(1 - 0.9^t), 0, 0) with t the optimizer's step count at iteration k and lr_k the schedule's rate (base_opt.py:352-357),
+ *     formed on the host.  losses[k] = the loss of iteration k, before its step.  Groups whose flag is off keep their bits.
+ *     niter == 0 does nothing.
+ *   points: get_pts3d and get_depthmaps (optimizer.py:164-186): pts3d [V][n][3], depth [V][n].
+ * ---------------------------------------------------------------------------------------------- */
+#define MI355GS_ALIGN_OPT_DEPTH 1       /* im_depthmaps.requires_grad */
+#define MI355GS_ALIGN_OPT_IM_POSES 2    /* im_poses.requires_grad: off after preset_pose (optimizer.py:66-81) */
+#define MI355GS_ALIGN_OPT_FOCALS 4      /* im_focals.requires_grad: off after preset_focal (optimizer.py:83-91) */
+#define MI355GS_ALIGN_OPT_PW_POSES 8    /* pw_poses.requires_grad */
+#define MI355GS_ALIGN_NORM_PW_SCALE 16  /* base_opt.py:176-182 get_pw_norm_scale_factor */
+size_t mi355gs_align_workspace_bytes(int V, int H, int W, int E, int flags);
+void* mi355gs_align_create(void* workspace, int V, int H, int W, const int32_t* edges, int E, int flags, float base_scale);
+void mi355gs_align_destroy(void* handle);
+/* optimizer.py:50-57 */
+int mi355gs_align_pack(void* handle, void* stream, const float* pred_i, const float* pred_j, const float* conf_i, const float* conf_j);
+/* optimizer.py:188-201 and its autograd */
+int mi355gs_align_grad(void* handle, void* stream, const float* depth_log, const float* im_pose, const float* focal_log, const float* pp_raw,
+                       const float* pw_pose, float* g_depth_log, float* g_im_pose, float* g_focal_log, float* g_pw_pose, float* loss);
+/* base_opt.py:326-366 */
+int mi355gs_align_run(void* handle, void* stream, int niter, const float* step_table, float* depth_log, float* im_pose, float* focal_log,
+                      const float* pp_raw, float* pw_pose, float* m_depth_log, float* v_depth_log, float* m_im_pose, float* v_im_pose,
+                      float* m_focal_log, float* v_focal_log, float* m_pw_pose, float* v_pw_pose, float* losses);
+/* optimizer.py:164-186 */
+int mi355gs_align_points(void* handle, void* stream, const float* depth_log, const float* im_pose, const float* focal_log,
+                         const float* pp_raw, const float* pw_pose, float* pts3d, float* depth);
+
 #ifdef __cplusplus
 }
 #endif

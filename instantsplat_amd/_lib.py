@@ -92,6 +92,13 @@ _SIGNATURES = {
     "mi355gs_covis_masks": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, _P]),
     "mi355gs_compact_scratch_bytes": (c_size_t, [c_int64]),
     "mi355gs_compact_pointmaps": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mi355gs_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "mi355gs_align_create": (c_void_p, [_P, c_int, c_int, c_int, _P, c_int, c_int, c_float]),
+    "mi355gs_align_destroy": (None, [_P]),
+    "mi355gs_align_pack": (c_int, [_P, _P, _P, _P, _P, _P]),
+    "mi355gs_align_grad": (c_int, [_P] * 12),
+    "mi355gs_align_run": (c_int, [_P, _P, c_int] + [_P] * 15),
+    "mi355gs_align_points": (c_int, [_P] * 9),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,0 +1,287 @@
+"""The global alignment loop — reference dust3r/cloud_opt/base_opt.py:326-366 (`global_alignment_loop`) over
+dust3r/cloud_opt/optimizer.py:188-201 (`PointCloudOptimizer.forward`): the stage that turns the network's pairwise pointmaps
+into one scene.  The reference runs it with 300 iterations for the training views (init_geo.py:48) and with 500 over training
+and test views together (init_test_pose.py:59).  Here the whole loop is ONE library call (csrc/align.hip, include/mi355gs.h
+mi355gs_align_*): three kernel dispatches per iteration, no host synchronisation, the Adam step of the depth maps applied in the
+kernel that forms their gradient.  There is no CPU fallback.
+
+  AlignProblem            the fixed side: edges, the packed pairwise pointmaps and confidences, the switches
+  AlignState              the five parameter tensors, the Adam moments, the step count; the reference's getters
+  from_reference_scene    reads a duck-typed reference `PointCloudOptimizer` (after `init_minimum_spanning_tree`) -> (problem, state)
+  global_alignment        the loop -> (last loss, losses[niter])
+
+Out of scope: the network, `init_minimum_spanning_tree` (roma's registration and cv2.solvePnPRansac; it runs once),
+`ModularPointCloudOptimizer`, `PairViewer`, `clean_pointcloud`, optimised pw_adaptors and principal points (both off in every
+InstantSplat script), images of different shapes within one problem."""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_VIEWS = 256
+MAX_EDGES = 65535
+MAX_ELEMENTS = 2 ** 31 - 1
+FOCAL_BREAK = 20.0     # reference optimizer.py:22
+PP_BREAK = 10.0        # reference optimizer.py:141-142
+OPT_DEPTH, OPT_IM_POSES, OPT_FOCALS, OPT_PW_POSES, NORM_PW_SCALE = 1, 2, 4, 8, 16   # include/mi355gs.h MI355GS_ALIGN_*
+
+
+def _f32(x, shape, what, dev):
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what} must be float32, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be {list(shape)}, got {list(t.shape)}")
+    _lib.require_device(t.contiguous())
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{what} is on {t.device}, the problem on {dev}")
+    return t.detach().contiguous()
+
+
+class AlignProblem:
+    """The fixed side of one alignment: V images of H x W, E directed edges (i, j) covering every image (any list: it need not
+    be symmetrised, an image may appear only as a j), the pairwise pointmaps pred_i / pred_j [E,H*W,3] (or [E,H,W,3]) and raw
+    confidences conf_i / conf_j [E,H*W] >= 1 (the reference's _stacked_pred_i / _j, conf_i / conf_j), and the switches: which
+    parameter groups take Adam steps (the reference's requires_grad: optimize_im_poses is off after `preset_pose`, which also
+    turns norm_pw_scale off; optimize_focals is off under --focal_avg / known_focal) and norm_pw_scale."""
+
+    def __init__(self, edges, pred_i, pred_j, conf_i, conf_j, H, W, *, optimize_depth=True, optimize_im_poses=True, optimize_focals=True,
+                 optimize_pw_poses=True, norm_pw_scale=True, base_scale=0.5):
+        edges = [(int(i), int(j)) for i, j in edges]
+        E, H, W = len(edges), int(H), int(W)
+        if E < 1 or H < 1 or W < 1:
+            raise ValueError(f"{E} edges over images of {H} x {W}: positive sizes expected")
+        V = max(max(e) for e in edges) + 1
+        n = H * W
+        for t in (pred_i, pred_j, conf_i, conf_j):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("pred_i, pred_j, conf_i, conf_j must be torch tensors on the device")
+        dev = _lib.require_device(pred_i.contiguous(), pred_j.contiguous(), conf_i.contiguous(), conf_j.contiguous())
+        for name, t in (("pred_i", pred_i), ("pred_j", pred_j)):
+            if t.dim() < 2 or t.shape[0] != E or t.numel() != E * n * 3:
+                raise ValueError(f"{name} must be [{E},{n},3]: images of different shapes within one problem are not taken; got {list(t.shape)}")
+        for name, t in (("conf_i", conf_i), ("conf_j", conf_j)):
+            if t.dim() < 1 or t.shape[0] != E or t.numel() != E * n:
+                raise ValueError(f"{name} must be [{E},{n}]: images of different shapes within one problem are not taken; got {list(t.shape)}")
+        self.flags = (OPT_DEPTH * bool(optimize_depth) | OPT_IM_POSES * bool(optimize_im_poses) | OPT_FOCALS * bool(optimize_focals)
+                      | OPT_PW_POSES * bool(optimize_pw_poses) | NORM_PW_SCALE * bool(norm_pw_scale))
+        self.V, self.H, self.W, self.E, self.edges, self.device, self.base_scale = V, H, W, E, edges, dev, float(base_scale)
+        self.conf_i = _f32(conf_i.reshape(E, n), (E, n), "conf_i", dev)
+        self.conf_j = _f32(conf_j.reshape(E, n), (E, n), "conf_j", dev)
+        pred_i = _f32(pred_i.reshape(E, n, 3), (E, n, 3), "pred_i", dev)
+        pred_j = _f32(pred_j.reshape(E, n, 3), (E, n, 3), "pred_j", dev)
+        L = _lib.lib()
+        nbytes = int(L.mi355gs_align_workspace_bytes(V, H, W, E, self.flags))
+        host_edges = (ctypes.c_int32 * (2 * E))(*[x for e in edges for x in e])
+        self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        self._handle = L.mi355gs_align_create(_lib.ptr(self._workspace), V, H, W, host_edges, E, self.flags, self.base_scale) if nbytes else None
+        if not self._handle:
+            self._handle = None
+            raise ValueError(f"mi355gs_align_create refused {V} images of {H} x {W} with {E} edges (include/mi355gs.h: V <= {MAX_VIEWS}, "
+                             f"E <= {MAX_EDGES}, E H W <= 2^31 - 1, every image covered by an edge, no edge from an image to itself)")
+        with _lib.on_device(dev):
+            _lib.check(L.mi355gs_align_pack(self._handle, _lib.stream_ptr(dev), _lib.ptr(pred_i), _lib.ptr(pred_j), _lib.ptr(self.conf_i),
+                                            _lib.ptr(self.conf_j)), "align_pack")
+            if dev.type == "cuda":
+                torch.cuda.current_stream(dev).synchronize()   # pred_i / pred_j may go once the records are written
+
+    @classmethod
+    def from_arrays(cls, *args, **kwargs):
+        return cls(*args, **kwargs)
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            try:
+                _lib.lib().mi355gs_align_destroy(h)
+            except Exception:
+                pass
+
+    def im_conf(self) -> torch.Tensor:
+        """`_compute_img_conf` (base_opt.py:137-143): per image the element-wise maximum of the raw confidences over every edge
+        side at which it occurs, [V,H,W]."""
+        out = torch.zeros(self.V, self.H * self.W, dtype=torch.float32, device=self.device)
+        for e, (i, j) in enumerate(self.edges):
+            out[i] = torch.maximum(out[i], self.conf_i[e])
+            out[j] = torch.maximum(out[j], self.conf_j[e])
+        return out.view(self.V, self.H, self.W)
+
+
+class AlignState:
+    """depth_log [V,H*W] (depth = exp), im_pose [V,7] (quaternion x y z w, then t; T = sign(t) expm1|t|), focal_log [V]
+    (focal = exp(focal_log / 20)), pp_raw [V,2] (constant; principal point = (W/2, H/2) + 10 pp_raw), pw_pose [E,8] (quaternion,
+    t, log-scale) — the reference's im_depthmaps, im_poses, im_focals, im_pp, pw_poses — with the Adam moments and step count."""
+    NAMES = ("depth_log", "im_pose", "focal_log", "pp_raw", "pw_pose")
+
+    def __init__(self, problem: AlignProblem, depth_log, im_pose, focal_log, pp_raw, pw_pose):
+        P, dev = problem, problem.device
+        self.problem = P
+        self.depth_log = _f32(depth_log.reshape(P.V, -1) if isinstance(depth_log, torch.Tensor) else depth_log, (P.V, P.H * P.W), "depth_log", dev).clone()
+        self.im_pose = _f32(im_pose, (P.V, 7), "im_pose", dev).clone()
+        self.focal_log = _f32(focal_log.reshape(-1) if isinstance(focal_log, torch.Tensor) else focal_log, (P.V,), "focal_log", dev).clone()
+        self.pp_raw = _f32(pp_raw, (P.V, 2), "pp_raw", dev).clone()
+        self.pw_pose = _f32(pw_pose, (P.E, 8), "pw_pose", dev).clone()
+        self.moments = {k: (torch.zeros_like(getattr(self, k)), torch.zeros_like(getattr(self, k))) for k in self.NAMES if k != "pp_raw"}
+        self.step = 0
+
+    @classmethod
+    def from_arrays(cls, problem, depth_log, im_pose, focal_log, pp_raw, pw_pose):
+        return cls(problem, depth_log, im_pose, focal_log, pp_raw, pw_pose)
+
+    def _state_ptrs(self):
+        return [_lib.ptr(getattr(self, k)) for k in self.NAMES]
+
+    # ---- the getters init_geo.py:51-59 reads, with the reference's meanings
+    def _poses(self, raw):
+        q = raw[:, :4] / raw[:, :4].norm(dim=1, keepdim=True)
+        x, y, z, w = q.unbind(1)
+        R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                         2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).view(-1, 3, 3)
+        t = raw[:, 4:7]
+        out = torch.zeros(raw.shape[0], 4, 4, dtype=raw.dtype, device=raw.device)
+        out[:, :3, :3], out[:, :3, 3], out[:, 3, 3] = R, torch.sign(t) * torch.expm1(t.abs()), 1
+        return out
+
+    def im_poses(self) -> torch.Tensor:
+        """`get_im_poses`: camera-to-world [V,4,4]"""
+        return self._poses(self.im_pose)
+
+    def focals(self) -> torch.Tensor:
+        """`get_focals`: [V,1]"""
+        return (self.focal_log.view(-1, 1) / FOCAL_BREAK).exp()
+
+    def principal_points(self) -> torch.Tensor:
+        P = self.problem
+        return torch.tensor([P.W / 2, P.H / 2], dtype=torch.float32, device=P.device) + PP_BREAK * self.pp_raw
+
+    def intrinsics(self) -> torch.Tensor:
+        """`get_intrinsics`: [V,3,3]"""
+        K = torch.zeros(self.problem.V, 3, 3, dtype=torch.float32, device=self.problem.device)
+        K[:, 0, 0] = K[:, 1, 1] = self.focals().flatten()
+        K[:, :2, 2] = self.principal_points()
+        K[:, 2, 2] = 1
+        return K
+
+    def _points(self):
+        P = self.problem
+        pts = torch.empty(P.V, P.H, P.W, 3, dtype=torch.float32, device=P.device)
+        depth = torch.empty(P.V, P.H, P.W, dtype=torch.float32, device=P.device)
+        with _lib.on_device(P.device):
+            _lib.check(_lib.lib().mi355gs_align_points(P._handle, _lib.stream_ptr(P.device), *self._state_ptrs(), _lib.ptr(pts), _lib.ptr(depth)),
+                       "align_points")
+        return pts, depth
+
+    def pts3d(self) -> torch.Tensor:
+        """`get_pts3d`: [V,H,W,3] (one kernel dispatch)"""
+        return self._points()[0]
+
+    def depthmaps(self) -> torch.Tensor:
+        """`get_depthmaps`: [V,H,W]"""
+        return self._points()[1]
+
+    def im_conf(self) -> torch.Tensor:
+        return self.problem.im_conf()
+
+    def to_init_stage_inputs(self, log_depth=False) -> dict:
+        """The keyword arrays `init_stage.init_from_pointmaps` takes from the aligner (init_geo.py:51-59): w2c = the inverse of
+        im_poses(), intrinsics, focals, pointmaps, depthmaps and confidences (im_conf()).  log_depth=True hands over
+        `im_depthmaps` as init_geo.py:56 does — the raw parameter, the LOG of the depth — instead of get_depthmaps()."""
+        P = self.problem
+        pts, depth = self._points()
+        return dict(pointmaps=pts, depthmaps=self.depth_log.view(P.V, P.H, P.W).clone() if log_depth else depth, confidences=self.im_conf(),
+                    intrinsics=self.intrinsics(), w2c=torch.linalg.inv(self.im_poses()).contiguous(), focals=self.focals().flatten())
+
+
+def from_reference_scene(scene):
+    """(problem, state) from a reference `PointCloudOptimizer` — duck-typed, nothing is imported from the reference — as it stands
+    after `global_aligner(...)` and `init_fun.init_minimum_spanning_tree(scene, ...)`, in place of `global_alignment_loop(scene)`.
+    Read: edges, _stacked_pred_i / _j, conf_i / conf_j, im_depthmaps, im_poses, im_focals, im_pp, pw_poses, pw_adaptors,
+    norm_pw_scale, base_scale, focal_break, pw_break and every parameter's requires_grad.  Refused with a ValueError naming the
+    switch: non-zero or trainable pw_adaptors (allow_pw_adaptors), trainable im_pp (optimize_pp), dist other than l1, a conf
+    transform other than log, a focal_break other than 20, images of different shapes."""
+    if getattr(scene.pw_adaptors, "requires_grad", False):
+        raise ValueError("allow_pw_adaptors=True (trainable pw_adaptors) is out of scope")
+    if bool((scene.pw_adaptors.detach() != 0).any()):
+        raise ValueError("non-zero pw_adaptors (allow_pw_adaptors) are out of scope")
+    if getattr(scene.im_pp, "requires_grad", False):
+        raise ValueError("optimize_pp=True (trainable im_pp) is out of scope")
+    probe_a, probe_b = torch.tensor([[3.0, 4.0, 0.0]]), torch.zeros(1, 3)
+    if not torch.allclose(torch.as_tensor(scene.dist(probe_a, probe_b, weight=torch.ones(1))).float(), torch.tensor([5.0])):
+        raise ValueError("dist: only dist='l1' (the weighted Euclidean norm) is implemented")
+    probe = torch.tensor([1.0, math.e, 7.5])
+    if not torch.allclose(torch.as_tensor(scene.conf_trf(probe)).float(), probe.log()):
+        raise ValueError("conf: only the conf='log' transform is implemented")
+    if float(scene.focal_break) != FOCAL_BREAK:
+        raise ValueError(f"focal_break = {scene.focal_break}: only {FOCAL_BREAK} is implemented")
+    float(scene.pw_break)   # only scales the adaptors, which are zero
+    shapes = {tuple(int(s) for s in hw) for hw in scene.imshapes}
+    if len(shapes) != 1:
+        raise ValueError(f"images of different shapes within one problem are not taken: {sorted(shapes)}")
+    H, W = shapes.pop()
+    edges = [(int(i), int(j)) for i, j in scene.edges]
+    names = [f"{i}_{j}" for i, j in edges]
+    conf_i = torch.stack([scene.conf_i[k].detach().reshape(-1) for k in names]).float()
+    conf_j = torch.stack([scene.conf_j[k].detach().reshape(-1) for k in names]).float()
+    problem = AlignProblem(edges, scene._stacked_pred_i.detach(), scene._stacked_pred_j.detach(), conf_i, conf_j, H, W,
+                           optimize_depth=scene.im_depthmaps.requires_grad, optimize_im_poses=scene.im_poses.requires_grad,
+                           optimize_focals=scene.im_focals.requires_grad, optimize_pw_poses=scene.pw_poses.requires_grad,
+                           norm_pw_scale=bool(scene.norm_pw_scale), base_scale=float(scene.base_scale))
+    state = AlignState(problem, scene.im_depthmaps.detach(), scene.im_poses.detach(), scene.im_focals.detach().reshape(-1),
+                       scene.im_pp.detach(), scene.pw_poses.detach())
+    return problem, state
+
+
+def step_table(first_step: int, niter: int, lr: float, schedule: str, lr_min: float) -> np.ndarray:
+    """float32 [niter,4]: row k = (-lr_k / (1 - 0.9^t), sqrt(1 - 0.9^t), 0, 0) with t = first_step + k + 1 and lr_k the schedule's
+    rate at k / niter (base_opt.py:352-357, commons.py:83-90), all formed in float64 as the reference and torch.optim.Adam do."""
+    if schedule not in ("cosine", "linear"):
+        raise ValueError(f"bad lr schedule={schedule!r}")
+    rows = np.zeros((niter, 4), dtype=np.float64)
+    for k in range(niter):
+        t = k / niter
+        lr_k = lr_min + (lr - lr_min) * (1 + np.cos(t * np.pi)) / 2 if schedule == "cosine" else lr + (lr_min - lr) * t
+        step = first_step + k + 1
+        bc1, bc2 = 1 - 0.9 ** step, 1 - 0.9 ** step
+        rows[k, 0], rows[k, 1] = -(lr_k / bc1), bc2 ** 0.5
+    return rows.astype(np.float32)
+
+
+def global_alignment(problem: AlignProblem, state: AlignState, niter=300, lr=0.01, schedule="cosine", lr_min=1e-6):
+    """`global_alignment_loop(net, lr, niter, schedule, lr_min)`: niter Adam iterations on `state`, in place, enqueued by one
+    library call (1 + 3 niter kernel dispatches).  -> (the loss of the last iteration, taken before that iteration's step, as a
+    float — the one synchronisation, after the run; losses float32 [niter] on the device).  niter = 0 leaves the state unchanged
+    and returns inf (base_opt.py:339)."""
+    if state.problem is not problem:
+        raise ValueError("the state belongs to another problem")
+    niter = int(niter)
+    if niter < 0:
+        raise ValueError(f"niter = {niter}")
+    dev = problem.device
+    losses = torch.empty(niter, dtype=torch.float32, device=dev)
+    if niter == 0 or not (problem.flags & (OPT_DEPTH | OPT_IM_POSES | OPT_FOCALS | OPT_PW_POSES)):
+        return float("inf"), losses[:0]   # (with nothing to optimise the reference returns before its loop, base_opt.py:327-329)
+    table = torch.from_numpy(step_table(state.step, niter, float(lr), schedule, float(lr_min))).to(dev)
+    moments = [_lib.ptr(t) for k in ("depth_log", "im_pose", "focal_log", "pw_pose") for t in state.moments[k]]
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().mi355gs_align_run(problem._handle, _lib.stream_ptr(dev), niter, _lib.ptr(table), *state._state_ptrs(), *moments,
+                                                _lib.ptr(losses)), "align_run")
+    state.step += niter
+    return float(losses[-1]), losses   # (the read of the last loss also keeps `table` alive until the run has finished)
+
+
+def gradients(problem: AlignProblem, state: AlignState) -> dict:
+    """The loss and every gradient at `state`, nothing updated (mi355gs_align_grad; tests)."""
+    dev = problem.device
+    g = {k: torch.empty_like(getattr(state, k)) for k in ("depth_log", "im_pose", "focal_log", "pw_pose")}
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().mi355gs_align_grad(problem._handle, _lib.stream_ptr(dev), *state._state_ptrs(), *[_lib.ptr(g[k]) for k in g],
+                                                 _lib.ptr(loss)), "align_grad")
+    g["loss"] = loss
+    return g
