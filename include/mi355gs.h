@@ -604,6 +604,45 @@ int mi355gs_align_run(void* handle, void* stream, int niter, const float* step_t
 /* optimizer.py:164-186 */
 int mi355gs_align_points(void* handle, void* stream, const float* depth_log, const float* im_pose, const float* focal_log,
                          const float* pp_raw, const float* pw_pose, float* pts3d, float* depth);
+/* the handle's records: device float [2 E][n][4], record (e, side) at index 2 e + side (side 0 = i), (x, y, z, log conf) */
+const float* mi355gs_align_records(void* handle);
+
+/* ----------------------------------------------------------------------------------------------
+ * The aligner's initialisation (reference dust3r/cloud_opt/init_im_poses.py:66-221 `init_minimum_spanning_tree` /
+ * `init_from_pts3d`, dust3r/post_process.py:36-53): the sums over the n = H W points of a pointmap.  The tree, the walk over it and
+ * which record feeds which image are the host's (instantsplat_amd/global_align.py).  Stateless calls on the caller's stream, device
+ * arrays, float, contiguous; no allocation, no memset, no float atomics, no host synchronisation; two calls give the same bits.
+ *
+ *   init_workspace_bytes(B, n): the scratch of any call below with B jobs (rows, images) of n points; 0 for B outside [1, 65535],
+ *     n < 1, n > 2^31 - 1025 or B n > 2^31 - 1.  Every call answers MI355GS_EINVAL for such sizes and for a null pointer.
+ *   A batch side is (base, idx, job_stride, pt_stride): job b reads base + (idx ? idx[b] : b) * job_stride floats, point p at
+ *     pt_stride * p (3: a pointmap; 4: the handle's records).  idx: device int32 [B] or null.
+ *   init_means: means[r] = mean(x[r][0 .. n)), rows of n floats (the confidence means behind commons.py:20-25).
+ *   init_register: per job the weighted similarity registration tgt ~ s R src + T with roma's rigid_points_registration(...,
+ *     compute_scaling = True) conventions: weighted centroids, M = sum w yh xh^T, R the special-orthogonal Procrustes solution
+ *     (last singular direction flipped when det < 0), s = (sum of the signed singular values) / sum w |xh|^2, T = cy - s R cx.
+ *     weights null: unit weights.  Two passes (centroids, then moments of the centred points), 4 launches.
+ *     srt [B][16]: s, R row-major [9], T [3], 0 0 0.  pw_pose [B][8] or null: quaternion (x y z w) of R, signed_log1p(T / s), log s.
+ *   init_apply: dst[p] = s R src[p] + T with (s, R, T) one srt row in device memory (null: a copy); dst [n][3].
+ *   init_focals: per job the Weiszfeld focal of `estimate_focal_knowing_depth` (principal point (W / 2, H / 2), closed-form start,
+ *     10 re-weightings, clipped at 0 from below): 22 launches for the whole batch.
+ *   init_state (init_im_poses.py:115-129): factor = norm_pw_scale ? exp(log(base_scale) - mean(pw_pose[:, 7])) : 1; pts3d
+ *     [V][n][3] *= factor in place; image v's pose is [R | factor T] of srt row pose_row[v] (< 0: identity); depth_log = log(z of
+ *     inv(pose) pts3d) with NaN and -inf -> 0, +inf -> FLT_MAX; im_pose = (quaternion of R, signed_log1p(T)); focal_log =
+ *     20 log(focal) with focal = focals[focal_row[v]] (focal_mode 0; focal_row < 0: 20 log(max(H, W))), the mean of those V values
+ *     (1) or known_focal (2).  V <= 256, E <= 65535.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_align_init_workspace_bytes(int B, int n);
+int mi355gs_align_init_means(void* workspace, void* stream, int rows, int n, const float* x, float* means);
+int mi355gs_align_init_register(void* workspace, void* stream, int B, int n, const float* src, const int32_t* src_idx, long long src_job_stride,
+                                int src_pt_stride, const float* tgt, const int32_t* tgt_idx, long long tgt_job_stride, const float* weights,
+                                const int32_t* w_idx, long long w_job_stride, float* srt, float* pw_pose);
+int mi355gs_align_init_apply(void* stream, int n, const float* src, int src_pt_stride, const float* srt, float* dst);
+int mi355gs_align_init_focals(void* workspace, void* stream, int B, int H, int W, const float* src, const int32_t* src_idx,
+                              long long src_job_stride, int src_pt_stride, float* focals);
+int mi355gs_align_init_state(void* workspace, void* stream, int V, int E, int H, int W, int norm_pw_scale, float base_scale, int focal_mode,
+                             float known_focal, const float* srt, const int32_t* pose_row, const float* focals, const int32_t* focal_row,
+                             const float* pw_pose, float* pts3d, float* depth_log, float* im_pose, float* focal_log);
 
 #ifdef __cplusplus
 }

@@ -99,6 +99,13 @@ _SIGNATURES = {
     "mi355gs_align_grad": (c_int, [_P] * 12),
     "mi355gs_align_run": (c_int, [_P, _P, c_int] + [_P] * 15),
     "mi355gs_align_points": (c_int, [_P] * 9),
+    "mi355gs_align_records": (c_void_p, [_P]),
+    "mi355gs_align_init_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355gs_align_init_means": (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    "mi355gs_align_init_register": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int64, c_int, _P, _P, c_int64, _P, _P, c_int64, _P, _P]),
+    "mi355gs_align_init_apply": (c_int, [_P, c_int, _P, c_int, _P, _P]),
+    "mi355gs_align_init_focals": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int64, c_int, _P]),
+    "mi355gs_align_init_state": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float] + [_P] * 9),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -663,4 +663,8 @@ int mi355gs_align_points(void* handle, void* stream_, const float* depth_log, co
   return MI355GS_OK;
 }
 
+const float* mi355gs_align_records(void* handle) {   // what align_init.hip's batches read as their sources
+  return handle ? (const float*)((Align*)handle)->recs : nullptr;
+}
+
 }  // extern "C"

@@ -9,8 +9,15 @@ kernel that forms their gradient.  There is no CPU fallback.
   AlignState              the five parameter tensors, the Adam moments, the step count; the reference's getters
   from_reference_scene    reads a duck-typed reference `PointCloudOptimizer` (after `init_minimum_spanning_tree`) -> (problem, state)
   global_alignment        the loop -> (last loss, losses[niter])
+  init_minimum_spanning_tree   the step in front of the loop (dust3r/cloud_opt/init_im_poses.py:66-221): edge scores, the tree and
+                          the walk over it (host decisions), V - 1 chained and E batched similarity registrations, Weiszfeld
+                          focals, scale normalisation and the state write-out (csrc/align_init.hip) -> AlignState
+  compute_global_alignment     the reference's entry point (base_opt.py:275-287): init="mst" or a caller's state, then the loop
+  register_points         the batched weighted similarity registration both stages call (roma's conventions)
+  spanning_tree, walk_plan     the host side of the initialisation, without scipy
 
-Out of scope: the network, `init_minimum_spanning_tree` (roma's registration and cv2.solvePnPRansac; it runs once),
+Out of scope: the network, cv2's RANSAC PnP (`pnp_fn` takes a caller's; the default is a deterministic registration, see
+`init_minimum_spanning_tree`), `init_from_known_poses` and the known-poses branch of `init_from_pts3d`,
 `ModularPointCloudOptimizer`, `PairViewer`, `clean_pointcloud`, optimised pw_adaptors and principal points (both off in every
 InstantSplat script), images of different shapes within one problem."""
 from __future__ import annotations
@@ -273,6 +280,247 @@ def global_alignment(problem: AlignProblem, state: AlignState, niter=300, lr=0.0
                                                 _lib.ptr(losses)), "align_run")
     state.step += niter
     return float(losses[-1]), losses   # (the read of the last loss also keeps `table` alive until the run has finished)
+
+
+# ------------------------------------------------------------------------------------------------ the initialisation (csrc/align_init.hip)
+def _init_workspace(dev, B, n):
+    nbytes = int(_lib.lib().mi355gs_align_init_workspace_bytes(int(B), int(n)))
+    if not nbytes:
+        raise ValueError(f"mi355gs_align_init_workspace_bytes refused {B} jobs of {n} points (include/mi355gs.h: 1 <= B <= {MAX_EDGES}, "
+                         f"n >= 1, B n <= 2^31 - 1)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def register_points(x, y, weights=None):
+    """The similarity registration y ~ scale * R x + T of B point sets, roma's `rigid_points_registration(x, y, weights,
+    compute_scaling=True)` conventions (weighted centroids; M = sum w yh xh^T; R the special-orthogonal Procrustes solution, the
+    last singular direction flipped when det < 0; scale = sum of the signed singular values / sum w |xh|^2).  x, y: float32
+    [B,n,3] on the device, weights [B,n] or None -> (scale [B], R [B,3,3], T [B,3]).  Four kernel dispatches, no synchronisation."""
+    for name, t in (("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"{name} must be a [B,n,3] tensor on the device")
+    B, n = int(x.shape[0]), int(x.shape[1])
+    if B < 1 or n < 1:
+        raise ValueError(f"{B} point sets of {n} points: positive sizes expected")
+    dev = _lib.require_device(x.contiguous())
+    x, y = _f32(x, (B, n, 3), "x", dev), _f32(y, (B, n, 3), "y", dev)
+    w = None if weights is None else _f32(weights, (B, n), "weights", dev)
+    ws = _init_workspace(dev, B, n)
+    srt = torch.empty(B, 16, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.lib().mi355gs_align_init_register(_lib.ptr(ws), _lib.stream_ptr(dev), B, n, _lib.ptr(x), None, 3 * n, 3, _lib.ptr(y), None,
+                                                          3 * n, _lib.ptr(w), None, n, _lib.ptr(srt), None), "align_init_register")
+    return srt[:, 0].clone(), srt[:, 1:10].reshape(B, 3, 3).clone(), srt[:, 10:13].clone()
+
+
+def spanning_tree(scores: dict, V: int) -> list:
+    """The tree `scipy.sparse.csgraph.minimum_spanning_tree` returns for the negated scores (init_im_poses.py:138-139), without
+    scipy: an image pair takes the better of its two directions, the tree keeps the spanning edges of the largest scores, and an
+    edge comes back in the direction that won.  -> [(score, i, j)].  The order among EQUAL scores is not pinned (neither is
+    scipy's): the first direction met and the first edge sorted win here."""
+    if V > MAX_VIEWS:
+        raise ValueError(f"{V} images: the host-side tree takes V <= {MAX_VIEWS}")
+    best = {}
+    for (i, j), s in scores.items():
+        key = (min(i, j), max(i, j))
+        if key not in best or s > best[key][0]:
+            best[key] = (s, i, j)
+    parent = list(range(V))
+
+    def root(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+    tree = []
+    for s, i, j in sorted(best.values(), key=lambda t: -t[0]):
+        ri, rj = root(i), root(j)
+        if ri != rj:
+            parent[ri] = rj
+            tree.append((s, i, j))
+    return tree
+
+
+def walk_plan(tree, edges, scores):
+    """The walk of init_im_poses.py:144-207 with the data left out: which records are copied, registered and applied in which
+    order, and which edge's pred_i feeds which image's focal.  -> dict(first=(e, i, j), steps=[(e, side, i, j)], mst_edges,
+    focal_edge={image: e}, pose_step={image: step index, or -1 for the identity of the first edge's i}).
+    side 0: i was done — pred_i[e] is registered onto pts3d[i] and pts3d[j] = s R pred_j[e] + T; side 1: the mirror image."""
+    eidx = {tuple(e): k for k, e in enumerate(edges)}
+    todo = sorted(tree)
+    _, i, j = todo.pop()                       # the strongest edge
+    cur = eidx[(i, j)]
+    first, done, mst = (cur, i, j), {i, j}, [(i, j)]
+    focal_edge, pose_step, steps = {i: cur}, {i: -1}, []
+    while todo:
+        score, i, j = todo.pop()
+        # The reference's quirk, reproduced: the focal of a not-yet-seen i is estimated from pred_i of the edge processed BEFORE
+        # this one (init_im_poses.py:166-167 reads `i_j` before the branches below reassign it), not from an edge of i.
+        if i not in focal_edge:
+            focal_edge[i] = cur
+        if i in done:
+            cur = eidx[(i, j)]
+            steps.append((cur, 0, i, j))
+            done.add(j)
+        elif j in done:
+            cur = eidx[(i, j)]
+            steps.append((cur, 1, i, j))
+            done.add(i)
+        else:
+            todo.insert(0, (score, i, j))      # touches neither end yet: back to the front of the queue
+            continue
+        mst.append((i, j))
+        if i not in pose_step:
+            pose_step[i] = len(steps) - 1
+    best_first = sorted(scores, key=lambda e: -scores[e])
+    best_edge_of = {}
+    for (i, j) in best_first:                  # the best-scoring edge whose first image is i
+        best_edge_of.setdefault(i, eidx[(i, j)])
+    for i, e in best_edge_of.items():
+        focal_edge.setdefault(i, e)
+    return dict(first=first, steps=steps, mst_edges=mst, focal_edge=focal_edge, pose_step=pose_step, best_edge_of=best_edge_of)
+
+
+def init_minimum_spanning_tree(problem: AlignProblem, *, focal_avg=False, known_focal=None, pnp_fn=None, min_conf_thr=3.0) -> AlignState:
+    """`init_fun.init_minimum_spanning_tree(scene, focal_avg=..., known_focal=...)` (init_im_poses.py:66-221) -> the state the
+    reference object holds afterwards (depth_log, im_pose, focal_log, zero pp_raw, pw_pose, fresh moments, step 0), ready for
+    `global_alignment`.  Also attached: `state.mst_edges` (the tree as directed edges, in the order the walk took them),
+    `state.init_pts3d` [V,H,W,3] (the initial world pointmaps, after scale normalisation), `state.focal_edge` ({image: the edge
+    whose pred_i fed its focal}), `state.init_focals` (those Weiszfeld estimates, in the order of sorted(focal_edge)) and
+    `state.edge_scores` ({edge: score}).
+
+    Everything is enqueued on the current stream.  There is ONE host synchronisation: the read of the 2 E confidence means the
+    tree is built from (the tree and the walk are host decisions; the V - 1 dependent registrations of the walk are chained on the
+    stream).  A second one happens only with `pnp_fn`.
+
+    Poses.  The walk gives at most V - 1 images a pose.  The reference fills the rest with `fast_pnp` (cv2.solvePnPRansac: random,
+    and not available here).  `pnp_fn(pts3d_i [H,W,3], focal, mask [H,W]) -> (focal, cam2world [4,4]) | None` takes a caller's
+    implementation under fast_pnp's contract (mask = im_conf[i] > min_conf_thr; None -> the identity, the reference's fallback).
+    THE DEFAULT (pnp_fn=None) DEPARTS FROM THE REFERENCE: a deterministic stand-in registers the image's own-frame pointmap
+    (pred_i of the best-scoring edge whose first image is i, weights conf_i) onto pts3d[i] and takes [R | T] — the step the walk's
+    own branches use, no synchronisation, no random sampling; an image that is never a first image gets the identity.  On
+    noise-free pointmaps both give the camera-to-world pose; they differ by what RANSAC's sampling and the registration's
+    least-squares fit make of the noise.
+
+    focal_avg / known_focal freeze the focals in the reference (`preset_focal`); a problem's switches are fixed when it is made,
+    so either is refused on a problem built without optimize_focals=False."""
+    P, L = problem, _lib.lib()
+    if not P.flags & OPT_IM_POSES:
+        raise ValueError("optimize_im_poses=False: the known-poses branch of init_from_pts3d (init_im_poses.py:95-106) is out of scope")
+    if (focal_avg or known_focal is not None) and P.flags & OPT_FOCALS:
+        raise ValueError("focal_avg / known_focal freeze the focals (preset_focal): build the AlignProblem with optimize_focals=False")
+    if known_focal is not None and not float(known_focal) > 0:
+        raise ValueError(f"known_focal = {known_focal}: a positive focal expected")
+    dev, V, E, n, H, W = P.device, P.V, P.E, P.H * P.W, P.H, P.W
+    st = _lib.stream_ptr(dev)
+    ws = _init_workspace(dev, max(E, V), n)
+    i32 = lambda values: torch.tensor(list(values), dtype=torch.int32).to(dev)   # noqa: E731
+    with _lib.on_device(dev):
+        means = torch.empty(2 * E, dtype=torch.float32, device=dev)
+        _lib.check(L.mi355gs_align_init_means(_lib.ptr(ws), st, E, n, _lib.ptr(P.conf_i), _lib.ptr(means)), "align_init_means")
+        _lib.check(L.mi355gs_align_init_means(_lib.ptr(ws), st, E, n, _lib.ptr(P.conf_j), _lib.ptr(means) + 4 * E), "align_init_means")
+        m = means.cpu().numpy()                                                  # the one synchronisation
+        scores = {e: float(m[k] * m[E + k]) for k, e in enumerate(P.edges)}      # commons.py:20-25
+        tree = spanning_tree(scores, V)
+        if len(tree) != V - 1:
+            raise ValueError("the edges do not connect every image: no spanning tree (the reference's walk would not end)")
+        plan = walk_plan(tree, P.edges, scores)
+        if focal_avg and len(plan["focal_edge"]) != V:
+            missing = sorted(set(range(V)) - set(plan["focal_edge"]))
+            raise ValueError(f"focal_avg: images {missing} are never the first image of an edge and have no focal estimate "
+                             "(the reference fails there too)")
+
+        # every index table is uploaded here, while the stream is idle: a host-to-device copy behind enqueued kernels would wait for them
+        n_steps = len(plan["steps"])
+        focal_images = sorted(plan["focal_edge"])
+        focal_row = {v: k for k, v in enumerate(focal_images)}
+        src_idx = i32(2 * plan["focal_edge"][v] for v in focal_images)
+        pair_src, pair_tgt = i32(2 * e for e in range(E)), i32(i for i, j in P.edges)
+        pose_row = [-1] * V
+        for v in range(V):
+            if v in plan["pose_step"]:
+                pose_row[v] = plan["pose_step"][v]
+            elif pnp_fn is None and v in plan["best_edge_of"]:
+                # the stand-in for PnP: the pair registration of the best edge of v IS the registration of v's own-frame pointmap
+                # onto pts3d[v] — its row of the pair batch is the pose
+                pose_row[v] = n_steps + plan["best_edge_of"][v]
+        if pnp_fn is None:
+            pose_row_d, focal_row_d = i32(pose_row), i32(focal_row.get(v, -1) for v in range(V))
+        recs = int(L.mi355gs_align_records(P._handle))
+        rec = lambda e, side: recs + 16 * n * (2 * e + side)                     # noqa: E731
+        pts3d = torch.empty(V, n, 3, dtype=torch.float32, device=dev)
+        img = lambda v: _lib.ptr(pts3d) + 12 * n * v                             # noqa: E731
+        srt = torch.zeros(n_steps + E + V, 16, dtype=torch.float32, device=dev)  # walk rows, pair rows, rows of pnp_fn
+        row = lambda k: _lib.ptr(srt) + 64 * k                                   # noqa: E731
+        e0, i0, j0 = plan["first"]
+        _lib.check(L.mi355gs_align_init_apply(st, n, rec(e0, 0), 4, None, img(i0)), "align_init_apply")
+        _lib.check(L.mi355gs_align_init_apply(st, n, rec(e0, 1), 4, None, img(j0)), "align_init_apply")
+        for k, (e, side, i, j) in enumerate(plan["steps"]):
+            known, new = (i, j) if side == 0 else (j, i)
+            conf = (P.conf_i if side == 0 else P.conf_j)[e]
+            _lib.check(L.mi355gs_align_init_register(_lib.ptr(ws), st, 1, n, rec(e, side), None, 0, 4, img(known), None, 0, _lib.ptr(conf), None, 0,
+                                                     row(k), None), "align_init_register")
+            _lib.check(L.mi355gs_align_init_apply(st, n, rec(e, 1 - side), 4, row(k), img(new)), "align_init_apply")
+
+        # focals: one batch over the images that have a source record (they do not depend on the walk's results)
+        focals = torch.zeros(len(focal_images) + V, dtype=torch.float32, device=dev)   # the estimates, then pnp_fn's
+        _lib.check(L.mi355gs_align_init_focals(_lib.ptr(ws), st, len(focal_images), H, W, recs, _lib.ptr(src_idx), 4 * n, 4, _lib.ptr(focals)),
+                   "align_init_focals")
+
+        # pair poses: every edge's pred_i onto pts3d[i], weights conf_i (init_im_poses.py:109-113)
+        pw_pose = torch.empty(E, 8, dtype=torch.float32, device=dev)
+        _lib.check(L.mi355gs_align_init_register(_lib.ptr(ws), st, E, n, recs, _lib.ptr(pair_src), 4 * n, 4, _lib.ptr(pts3d), _lib.ptr(pair_tgt),
+                                                 3 * n, _lib.ptr(P.conf_i), None, n, row(n_steps), _lib.ptr(pw_pose)), "align_init_register")
+
+        if pnp_fn is not None:
+            im_conf, host_focals = P.im_conf(), None
+            for v in range(V):
+                if v in plan["pose_step"]:
+                    continue
+                if host_focals is None:
+                    host_focals = focals.cpu()                                   # the second synchronisation
+                focal = float(host_focals[focal_row[v]]) if v in focal_row else None
+                res = pnp_fn(pts3d[v].view(H, W, 3), focal, im_conf[v] > min_conf_thr)
+                if not res:
+                    continue                                                     # the identity (init_im_poses.py:215-216)
+                focal, cam2world = res
+                c2w = torch.as_tensor(cam2world, dtype=torch.float32).reshape(4, 4).cpu()
+                pose_row[v] = n_steps + E + v
+                srt[pose_row[v]] = torch.cat([torch.ones(1), c2w[:3, :3].reshape(9), c2w[:3, 3], torch.zeros(3)]).to(dev)
+                focal_row[v] = len(focal_images) + v
+                focals[focal_row[v]] = float(focal)
+
+        depth_log = torch.empty(V, n, dtype=torch.float32, device=dev)
+        im_pose = torch.empty(V, 7, dtype=torch.float32, device=dev)
+        focal_log = torch.empty(V, dtype=torch.float32, device=dev)
+        if pnp_fn is not None:
+            pose_row_d, focal_row_d = i32(pose_row), i32(focal_row.get(v, -1) for v in range(V))
+        mode = 2 if known_focal is not None else (1 if focal_avg else 0)
+        _lib.check(L.mi355gs_align_init_state(_lib.ptr(ws), st, V, E, H, W, 1 if P.flags & NORM_PW_SCALE else 0, P.base_scale, mode,
+                                              float(known_focal) if known_focal is not None else 0.0, _lib.ptr(srt), _lib.ptr(pose_row_d),
+                                              _lib.ptr(focals), _lib.ptr(focal_row_d), _lib.ptr(pw_pose), _lib.ptr(pts3d), _lib.ptr(depth_log),
+                                              _lib.ptr(im_pose), _lib.ptr(focal_log)), "align_init_state")
+        state = AlignState(P, depth_log, im_pose, focal_log, torch.zeros(V, 2, dtype=torch.float32, device=dev), pw_pose)
+    state.mst_edges, state.init_pts3d, state.focal_edge, state.edge_scores = plan["mst_edges"], pts3d.view(V, H, W, 3), dict(plan["focal_edge"]), scores
+    state.init_focals = focals[:len(focal_images)]   # the per-image Weiszfeld estimates, in the order of sorted(focal_edge)
+    return state
+
+
+def compute_global_alignment(problem: AlignProblem, init="mst", niter=300, schedule="cosine", lr=0.01, lr_min=1e-6, focal_avg=False,
+                             known_focal=None, pnp_fn=None, state=None):
+    """`compute_global_alignment` (base_opt.py:275-287): the initialisation, then the loop -> (state, last loss, losses).
+    init="mst": `init_minimum_spanning_tree`; init=None: the caller's `state` as it stands; init="known_poses" is out of scope."""
+    if init == "mst":
+        state = init_minimum_spanning_tree(problem, focal_avg=focal_avg, known_focal=known_focal, pnp_fn=pnp_fn)
+    elif init == "known_poses":
+        raise ValueError("init='known_poses' (init_from_known_poses) is out of scope")
+    elif init is None:
+        if state is None:
+            raise ValueError("init=None takes the caller's state: pass state=")
+    else:
+        raise ValueError(f"bad value for init={init!r}")
+    last, losses = global_alignment(problem, state, niter=niter, lr=lr, schedule=schedule, lr_min=lr_min)
+    return state, last, losses
 
 
 def gradients(problem: AlignProblem, state: AlignState) -> dict:
