@@ -519,6 +519,30 @@ int mi355gs_metrics_rgb8(void* stream, int N, int H, int W, const uint8_t* a, co
                          float* ssim_mean);
 
 /* ----------------------------------------------------------------------------------------------
+ * PNG files of 8-bit RGB frames, encoded on the device (csrc/png.hip).  frames: uint8 [N][H][W][3] in device memory, any base
+ * address (a slice of a stack is fine).  out receives the N files back to back: file i is out[offsets[i] : offsets[i+1]], offsets
+ * a device array of N + 1.  Every file is: signature, IHDR (8-bit RGB, no interlace), one IDAT per block of rows_per_block
+ * filtered rows (0: the largest R with R (3 W + 1) <= 65536, at least 1; the last block holds the remaining rows), one IDAT with
+ * the 4 Adler-32 bytes, IEND.  Every row is Paeth-filtered (filter byte 4).  A block is one dynamic-Huffman deflate block of
+ * literals only (no LZ77 matches: what zlib's Z_HUFFMAN_ONLY produces) under an OPTIMAL code of at most 15 bits per symbol
+ * (minimum sum of count x length over the block's 256 literals and the end-of-block symbol), followed by an empty stored block,
+ * so that every block ends on a byte; the zlib header 78 01 opens the first block's chunk.  The price of leaving matches out is
+ * a floor of one bit per byte: a constant-colour frame comes to 1/8 of its raw size.
+ *   Size: a block of n filtered bytes gives at most (2 for a frame's first) + ceil((1106 + 9 (n + 1) + 3) / 8) + 4 data bytes;
+ *   mi355gs_png_rgb8_stream_bytes is that bound over all N files with their framing, the size `out` must have.  The bytes of
+ *   `out` behind offsets[N] are not written.
+ * Three launches per call whatever N is, on the caller's stream; no host synchronisation, no allocation, no memset.  scratch: the
+ * scratch-size query's bytes of device memory, 16-byte aligned, owned by the caller.  Both queries return 0 for sizes the call
+ * refuses.  Limits (MI355GS_EINVAL beyond them, as for null pointers, non-positive sizes, a negative rows_per_block, a scratch
+ * pointer that is not 16-byte aligned and an offsets pointer that is not 8-byte aligned): N <= 65535, W <= 21845,
+ * rows_per_block (3 W + 1) <= 65536, N x ceil(H / rows_per_block) <= 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_png_rgb8_scratch_bytes(int N, int H, int W, int rows_per_block);
+size_t mi355gs_png_rgb8_stream_bytes(int N, int H, int W, int rows_per_block);
+int mi355gs_png_rgb8(void* stream, int N, int H, int W, int rows_per_block, const uint8_t* frames, void* scratch, uint8_t* out,
+                     int64_t* offsets);
+
+/* ----------------------------------------------------------------------------------------------
  * The tail of the init stage (reference init_geo.py:61-129 behind `compute_global_alignment`; utils/sfm_utils.py:250-432):
  * confidence statistics, co-visibility masks and the ordered compaction of V aligned pointmaps.  All arrays are device memory,
  * contiguous: pointmaps float [V][H][W][3], depthmaps / confidences float [V][H][W], images float [V][H][W][3] in [0,1],

@@ -240,15 +240,17 @@ def render_set_optimize(views: List, gaussians, pipe, background, num_iter: int 
 
 
 def render_test_set(model_path, iteration, views: List, gaussians, pipe, background, num_iter: int = 500, fused: bool = True,
-                    init_poses=None) -> dict:
+                    init_poses=None, png: str = "pil") -> dict:
     """The file-writing form of reference render.py:99-170: every view tracked by `render_set_optimize`, its final render and
     `view.original_image[0:3]` quantised as torchvision.utils.save_image does (render_path.quantize_rgb8) and written to
-    <model_path>/test/ours_<iteration>/renders/<image_name>.png and .../gt/<image_name>.png.
+    <model_path>/test/ours_<iteration>/renders/<image_name>.png and .../gt/<image_name>.png.  png="device" encodes both sets of
+    files on the GPU (instantsplat_amd/png.py) from the stacks that are already there; "pil" is the reference's writer.
     -> dict(results = the tracker's per-view dicts,
             frames = {"ours_<iteration>": [dict(names = file names, renders = uint8 [n,H,W,3], gts = uint8 [n,H,W,3]), ...]}:
             the two frame stacks as device tensors, one entry per image size — what `metrics.evaluate(model_path, frames=...)`
             scores without reading the files back)."""
-    from .render_path import _save_png, quantize_rgb8
+    from .render_path import _check_png, _save_png, quantize_rgb8
+    device_png = _check_png(png)
     views = list(views)
     method = f"ours_{iteration}"
     base = os.path.join(str(model_path), "test", method)
@@ -267,6 +269,10 @@ def render_test_set(model_path, iteration, views: List, gaussians, pipe, backgro
     groups = [dict(names=g["names"], renders=torch.stack(g["renders"]), gts=torch.stack(g["gts"])) for g in by_size.values()]
     for g in groups:   # one device-to-host copy per stack
         for stack, d in ((g["renders"], render_dir), (g["gts"], gts_dir)):
+            if device_png:
+                from .png import write_png_files
+                write_png_files([os.path.join(d, name) for name in g["names"]], stack)
+                continue
             for name, frame in zip(g["names"], stack.cpu().numpy()):
                 _save_png(os.path.join(d, name), frame)
     return dict(results=results, frames={method: groups})

@@ -203,25 +203,52 @@ def _save_png(path: str, hwc: np.ndarray):
     Image.fromarray(hwc).save(path)   # (what torchvision.utils.save_image does with the bytes it has quantised)
 
 
-def render_set(model_path, name: str, iteration, views: List, gaussians, pipe, background, fused: bool = True) -> str:
+def _check_png(png: str) -> bool:
+    """the `png=` argument of the file-writing stages -> True for the device encoder (instantsplat_amd/png.py)"""
+    if png not in ("pil", "device"):
+        raise ValueError(f'png must be "pil" (PIL on the host) or "device" (instantsplat_amd.png on the GPU), got {png!r}')
+    return png == "device"
+
+
+def _write_png_device(paths: List[str], frames: List[torch.Tensor]):
+    """uint8 [H,W,3] device frames to files through the device encoder: one encode per image size"""
+    from .png import write_png_files
+    by_size = {}
+    for path, frame in zip(paths, frames):
+        grp = by_size.setdefault(tuple(frame.shape), ([], []))
+        grp[0].append(path); grp[1].append(frame)
+    for group_paths, group in by_size.values():
+        write_png_files(group_paths, torch.stack(group))
+
+
+def render_set(model_path, name: str, iteration, views: List, gaussians, pipe, background, fused: bool = True, png: str = "pil") -> str:
     """reference render.py:78-97: <model_path>/<name>/ours_<iteration>/renders/{idx:05d}.png for every view and, unless name is
-    "interp", gt/{idx:05d}.png.  fused=False renders frame by frame with render() and quantize_rgb8.  Returns the renders'
-    directory."""
+    "interp", gt/{idx:05d}.png.  fused=False renders frame by frame with render() and quantize_rgb8.  png="device" encodes the
+    files on the GPU (instantsplat_amd/png.py: the same pixels in larger files, without PIL's host time per frame); "pil" is
+    the reference's writer.  Returns the renders' directory."""
+    device_png = _check_png(png)
     views = list(views)
     base = os.path.join(str(model_path), name, f"ours_{iteration}")
     render_dir, gts_dir = os.path.join(base, "renders"), os.path.join(base, "gt")
     os.makedirs(render_dir, exist_ok=True)
     os.makedirs(gts_dir, exist_ok=True)
+    to_host = (lambda f: f) if device_png else (lambda f: f.cpu().numpy())
     if fused:
         frames = render_pose_path(views, gaussians, pipe, background)["frames"]
-        frames = [f.cpu().numpy() for f in frames] if isinstance(frames, list) else [frames.cpu().numpy()]
+        frames = [to_host(f) for f in frames] if isinstance(frames, list) else [to_host(frames)]
         frames = [f for group in frames for f in group]
     else:
         frames = []
         with torch.no_grad():
             for view in views:
                 pose = get_tensor_from_camera(view.world_view_transform.transpose(0, 1).cpu()).to(gaussians.get_xyz.device)
-                frames.append(quantize_rgb8(render(view, gaussians, pipe, background, camera_pose=pose)["render"]).cpu().numpy())
+                frames.append(to_host(quantize_rgb8(render(view, gaussians, pipe, background, camera_pose=pose)["render"])))
+    if device_png:
+        _write_png_device([os.path.join(render_dir, f"{idx:05d}.png") for idx in range(len(views))], frames)
+        if name != "interp":
+            gts = [quantize_rgb8(view.original_image[0:3].to(gaussians.get_xyz.device).float().contiguous()) for view in views]
+            _write_png_device([os.path.join(gts_dir, f"{idx:05d}.png") for idx in range(len(views))], gts)
+        return render_dir
     for idx, (view, frame) in enumerate(zip(views, frames)):
         _save_png(os.path.join(render_dir, f"{idx:05d}.png"), frame)
         if name != "interp":
@@ -242,16 +269,19 @@ def images_to_video(image_folder: str, output_video_path: str, fps: int = 30) ->
     return True
 
 
-def render_interpolated(model_path, iteration, n_views: int, train_cameras: List, gaussians, pipe, background, fused: bool = True) -> str:
+def render_interpolated(model_path, iteration, n_views: int, train_cameras: List, gaussians, pipe, background, fused: bool = True,
+                        png: str = "pil") -> str:
     """The `--infer_video` stage (reference render.py:233-248): pose_interpolated.npy from the optimised poses, the training cameras
     repeated along it, every pose rendered to interp/ours_<iteration>/renders/, and interp_<n_views>_view.mp4 beside that
-    directory if imageio is installed (otherwise a message says that the video was skipped).  Returns the frame directory."""
+    directory if imageio is installed (otherwise a message says that the video was skipped).  png: as for `render_set`.  Returns
+    the frame directory."""
+    _check_png(png)
     pose_file = save_interpolate_pose(model_path, iteration, n_views)
     cams = [copy.copy(c) for c in train_cameras]
     for c in cams:   # load_cameras copies every camera it repeats along the path; the "interp" set writes no ground truth
         c.original_image = None
     views = load_cameras(np.load(pose_file), cams)
-    render_dir = render_set(model_path, "interp", iteration, views, gaussians, pipe, background, fused=fused)
+    render_dir = render_set(model_path, "interp", iteration, views, gaussians, pipe, background, fused=fused, png=png)
     video = os.path.join(str(model_path), "interp", f"ours_{iteration}", f"interp_{n_views}_view.mp4")
     if images_to_video(render_dir, video):
         print(f"wrote {len(views)} frames and {video}")
