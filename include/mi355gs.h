@@ -543,6 +543,33 @@ int mi355gs_png_rgb8(void* stream, int N, int H, int W, int rows_per_block, cons
                      int64_t* offsets);
 
 /* ----------------------------------------------------------------------------------------------
+ * Baseline JPEG files of 8-bit RGB frames, encoded on the device (csrc/jpeg.hip): the frames of a Motion-JPEG video
+ * (instantsplat_amd/video.py).  frames: uint8 [N][H][W][3] in device memory, any base address.  subsampling: 0 = 4:4:4, 2 = 4:2:0.
+ * qtables: HOST array of 2 x 64 bytes, luma then chroma, natural (row-major) order, every entry 1..255; read during the call.
+ * Every file is, in libjpeg's order: SOI, APP0 (JFIF 1.01, units 0, density 1 x 1), DQT 0 and DQT 1, SOF0 (components 1, 2, 3;
+ * Y sampled 2 x 2 at 4:2:0; tables 0, 1, 1), DHT DC 0 / AC 0 / DC 1 / AC 1 (the typical tables of Annex K.3), DRI = the MCUs of
+ * one MCU row, SOS, the entropy-coded data with RST0..RST7 in front of every MCU row but the first, EOI.  The arithmetic is
+ * libjpeg's integer arithmetic throughout (16-bit fixed-point colour conversion, edge replication, h2v2 downsampling with the
+ * alternating bias, the `islow` forward DCT, quantisation by truncating division of the rounded magnitude): the file equals,
+ * byte for byte, what libjpeg / libjpeg-turbo write for the same tables with optimize off and one restart interval per MCU row.
+ *   Capacity protocol: out receives the files back to back, file i at out[offsets[i] : offsets[i+1]].  offsets (device, N + 1) is
+ *   ALWAYS exact, whatever out_bytes is.  File i is written — whole — exactly when offsets[i+1] <= out_bytes; no byte at or beyond
+ *   out + out_bytes is ever written (out_bytes may be 0).  A caller may therefore pass a speculative buffer and encode the frames
+ *   that did not fit again with the exact size.  mi355gs_jpeg_rgb8_stream_bytes is the worst case over all contents, framing
+ *   included: per MCU row 2 x ceil(blocks x 1660 / 8) (1660 bits: a block's longest code; x 2: a zero behind every FF byte).
+ * Three launches per call whatever N is (transform + count per MCU row; one scan; pack + store per MCU row), on the caller's
+ * stream; no host synchronisation, no allocation, no memset.  scratch: the scratch-size query's bytes of device memory (the
+ * quantised coefficients, 2 bytes each), 16-byte aligned, owned by the caller.  Both queries return 0 for sizes the call refuses.
+ * Limits (MI355GS_EINVAL beyond them, as for null pointers, non-positive sizes, a subsampling other than 0 or 2, a table entry of
+ * 0, a scratch pointer that is not 16-byte aligned and an offsets pointer that is not 8-byte aligned): H, W <= 65535 (the
+ * format's), N <= 65535, 3 H W <= 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_jpeg_rgb8_scratch_bytes(int N, int H, int W, int subsampling);
+size_t mi355gs_jpeg_rgb8_stream_bytes(int N, int H, int W, int subsampling);
+int mi355gs_jpeg_rgb8(void* stream, int N, int H, int W, int subsampling, const uint8_t* qtables, const uint8_t* frames, void* scratch,
+                      uint8_t* out, size_t out_bytes, int64_t* offsets);
+
+/* ----------------------------------------------------------------------------------------------
  * The tail of the init stage (reference init_geo.py:61-129 behind `compute_global_alignment`; utils/sfm_utils.py:250-432):
  * confidence statistics, co-visibility masks and the ordered compaction of V aligned pointmaps.  All arrays are device memory,
  * contiguous: pointmaps float [V][H][W][3], depthmaps / confidences float [V][H][W], images float [V][H][W][3] in [0,1],

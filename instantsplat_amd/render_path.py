@@ -13,7 +13,7 @@ import copy
 import ctypes
 import math
 import os
-from typing import List
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -221,11 +221,13 @@ def _write_png_device(paths: List[str], frames: List[torch.Tensor]):
         write_png_files(group_paths, torch.stack(group))
 
 
-def render_set(model_path, name: str, iteration, views: List, gaussians, pipe, background, fused: bool = True, png: str = "pil") -> str:
+def render_set(model_path, name: str, iteration, views: List, gaussians, pipe, background, fused: bool = True, png: str = "pil", *,
+               frames_out: Optional[list] = None) -> str:
     """reference render.py:78-97: <model_path>/<name>/ours_<iteration>/renders/{idx:05d}.png for every view and, unless name is
     "interp", gt/{idx:05d}.png.  fused=False renders frame by frame with render() and quantize_rgb8.  png="device" encodes the
     files on the GPU (instantsplat_amd/png.py: the same pixels in larger files, without PIL's host time per frame); "pil" is
-    the reference's writer.  Returns the renders' directory."""
+    the reference's writer.  frames_out: a list that receives the rendered uint8 [H,W,3] frames as they stand in device memory,
+    in view order (the video of `render_interpolated` is made of them).  Returns the renders' directory."""
     device_png = _check_png(png)
     views = list(views)
     base = os.path.join(str(model_path), name, f"ours_{iteration}")
@@ -235,14 +237,19 @@ def render_set(model_path, name: str, iteration, views: List, gaussians, pipe, b
     to_host = (lambda f: f) if device_png else (lambda f: f.cpu().numpy())
     if fused:
         frames = render_pose_path(views, gaussians, pipe, background)["frames"]
-        frames = [to_host(f) for f in frames] if isinstance(frames, list) else [to_host(frames)]
-        frames = [f for group in frames for f in group]
+        frames = frames if isinstance(frames, list) else [frames]
+        if frames_out is not None:
+            frames_out.extend(f for group in frames for f in group)
+        frames = [f for group in frames for f in to_host(group)]
     else:
         frames = []
         with torch.no_grad():
             for view in views:
                 pose = get_tensor_from_camera(view.world_view_transform.transpose(0, 1).cpu()).to(gaussians.get_xyz.device)
-                frames.append(to_host(quantize_rgb8(render(view, gaussians, pipe, background, camera_pose=pose)["render"])))
+                frame = quantize_rgb8(render(view, gaussians, pipe, background, camera_pose=pose)["render"])
+                if frames_out is not None:
+                    frames_out.append(frame)
+                frames.append(to_host(frame))
     if device_png:
         _write_png_device([os.path.join(render_dir, f"{idx:05d}.png") for idx in range(len(views))], frames)
         if name != "interp":
@@ -269,18 +276,41 @@ def images_to_video(image_folder: str, output_video_path: str, fps: int = 30) ->
     return True
 
 
+def write_mjpeg_video(path: str, frames: List[torch.Tensor], quality=90, fps=30) -> None:
+    """uint8 [H,W,3] device frames of one size -> an AVI file of 4:2:0 JPEG frames encoded on the device (instantsplat_amd/jpeg.py,
+    instantsplat_amd/video.py)"""
+    from .jpeg import encode_jpeg_rgb8
+    from .video import write_mjpeg_avi
+    if not frames or any(f.shape != frames[0].shape for f in frames):
+        raise ValueError("a video needs at least one frame, and all frames of one size")
+    enc = encode_jpeg_rgb8(torch.stack(list(frames)), quality=quality, subsampling="4:2:0")
+    H, W = (int(s) for s in frames[0].shape[:2])
+    write_mjpeg_avi(path, enc["stream"], enc["offsets"], W, H, fps=fps)
+
+
 def render_interpolated(model_path, iteration, n_views: int, train_cameras: List, gaussians, pipe, background, fused: bool = True,
-                        png: str = "pil") -> str:
+                        png: str = "pil", video: str = "imageio", video_quality=90) -> str:
     """The `--infer_video` stage (reference render.py:233-248): pose_interpolated.npy from the optimised poses, the training cameras
     repeated along it, every pose rendered to interp/ours_<iteration>/renders/, and interp_<n_views>_view.mp4 beside that
-    directory if imageio is installed (otherwise a message says that the video was skipped).  png: as for `render_set`.  Returns
-    the frame directory."""
+    directory if imageio is installed (otherwise a message says that the video was skipped).  png: as for `render_set`.
+    video="mjpeg" writes interp_<n_views>_view.avi instead, 30 frames per second of Motion-JPEG at `video_quality` (4:2:0), encoded
+    on the device from the frames the path renderer left there — the PNG files are written as `png` says, and not read back.
+    Returns the frame directory."""
     _check_png(png)
+    if video not in ("imageio", "mjpeg"):
+        raise ValueError(f'video must be "imageio" (an mp4 through imageio, if installed) or "mjpeg" (an AVI encoded on the GPU), got {video!r}')
     pose_file = save_interpolate_pose(model_path, iteration, n_views)
     cams = [copy.copy(c) for c in train_cameras]
     for c in cams:   # load_cameras copies every camera it repeats along the path; the "interp" set writes no ground truth
         c.original_image = None
     views = load_cameras(np.load(pose_file), cams)
+    if video == "mjpeg":
+        device_frames: list = []
+        render_dir = render_set(model_path, "interp", iteration, views, gaussians, pipe, background, fused=fused, png=png, frames_out=device_frames)
+        avi = os.path.join(str(model_path), "interp", f"ours_{iteration}", f"interp_{n_views}_view.avi")
+        write_mjpeg_video(avi, device_frames, quality=video_quality, fps=30)
+        print(f"wrote {len(views)} frames and {avi}")
+        return render_dir
     render_dir = render_set(model_path, "interp", iteration, views, gaussians, pipe, background, fused=fused, png=png)
     video = os.path.join(str(model_path), "interp", f"ours_{iteration}", f"interp_{n_views}_view.mp4")
     if images_to_video(render_dir, video):
