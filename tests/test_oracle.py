@@ -22,6 +22,7 @@ from instantsplat_amd.camera import Camera
 from instantsplat_amd.synthetic import syn_blob
 from oracle import gs_ref
 from oracle import raster_torch as rt
+from tests import projection_cases as pc
 from tests.util import settings_for
 
 F64 = torch.float64
@@ -39,10 +40,12 @@ def _blob_inputs(P, W, H, seed, scale_mean, dtype):
     return sc.camera, {k: v.to(dtype) for k, v in d.items()}
 
 
-def _run(which, cam, inp, deg, dtype, wgt, precomp_color=False, precomp_cov=False, mod=1.0, bg=(0.2, 0.5, 0.9)):
-    """One forward + backward through the C oracle ("c") or the dense autograd restatement ("torch")."""
+def _run(which, cam, inp, deg, dtype, wgt, precomp_color=False, precomp_cov=False, mod=1.0, bg=(0.2, 0.5, 0.9), st=None):
+    """One forward + backward through the C oracle ("c") or the dense autograd restatement ("torch"); st: settings other than
+    the identity view's."""
     bg_t = torch.tensor(bg, dtype=torch.float32)
-    st = _settings64(cam, deg, bg_t, mod) if dtype == F64 else settings_for(cam, deg, rt.RasterSettings, bg_t, mod=mod)
+    if st is None:
+        st = _settings64(cam, deg, bg_t, mod) if dtype == F64 else settings_for(cam, deg, rt.RasterSettings, bg_t, mod=mod)
     lv = {k: v.clone().to(dtype).requires_grad_(True) for k, v in inp.items()}
     m2d = torch.zeros(lv["means3D"].shape[0], 3, dtype=dtype, requires_grad=True)
     kw = {}
@@ -100,6 +103,26 @@ def test_c_oracle_equals_autograd_restatement_f64(case):
         assert _rel(c_g[k], t_g[k]) <= 1e-10, (k, _rel(c_g[k], t_g[k]))
 
 
+@pytest.mark.parametrize("camera", [c for c in pc.CAMERAS if c != "identity"])
+@pytest.mark.parametrize("family", pc.FAMILIES)
+def test_c_oracle_equals_autograd_restatement_f64_general_cameras(family, camera):
+    """The same statement off the identity view: every family of tests/projection_cases.py (the EWA clamp, every SH clamp pattern,
+    precomputed covariances and colours, scale_modifier 1.7 in the exact convention, un-normalised quaternions) under every
+    non-identity camera — W with all nine entries, with a negative diagonal, identity W with campos != 0, campos = 0.  The device
+    tests of that file are judged against gs_ref.c; this is what ties gs_ref.c to autograd there.  Measured: image 2e-15, gradients 6e-15 per tensor, 6e-13 in the
+    worst row."""
+    case = pc.oracle_case(family, camera)
+    c, t = pc.run_reference(case, F64, "c"), pc.run_reference(case, F64, "torch")
+    assert torch.equal(c["radii"], t["radii"]) and torch.equal(c["radii"] > 0, pc.geometry(case)["visible"])
+    assert int((c["radii"] > 0).sum()) >= (case.P // 4 if family != "block_edges" else 2)
+    assert float((c["color"] - t["color"]).abs().max()) <= 1e-12
+    assert set(c["grads"]) == set(t["grads"])
+    for k in c["grads"]:
+        assert float(t["grads"][k].abs().max()) > 0, k
+        assert _rel(c["grads"][k], t["grads"][k]) <= 1e-10, (k, _rel(c["grads"][k], t["grads"][k]))
+        assert float(pc.row_errors(c["grads"][k], t["grads"][k]).max()) <= 1e-9, k      # ... and row by row
+
+
 def test_c_oracle_scale_grad_conventions_f64():
     """scale_modifier = 0.7 in both conventions of dL/dscale: the default (the published operator's dL/d(mod * scale), checked
     against the restatement above through CASES[2]) and the true derivative (autograd's own), which is mod times the default."""
@@ -145,7 +168,7 @@ def _tiny_scene(kind):
     fovx = math.radians(60.0)
     tanx = math.tan(fovx / 2)
     cam = Camera(0, torch.eye(4), fovx, 2 * math.atan(tanx * H / W), W, H)
-    g = torch.Generator().manual_seed({"generic": 11, "sh_clamp": 12, "ewa_clamp": 13, "alpha_clamp": 14}[kind])
+    g = torch.Generator().manual_seed({"generic": 11, "sh_clamp": 12, "ewa_clamp": 13, "alpha_clamp": 14, "generic_camera": 11}[kind])
     P = 6
     z = 3.0 + 2.0 * torch.rand(P, generator=g, dtype=F64)
     x = (torch.rand(P, generator=g, dtype=F64) - 0.5) * 1.2 * tanx * z
@@ -177,12 +200,23 @@ def _tiny_scene(kind):
         means[3] = torch.tensor([0.1, -0.05, 3.5], dtype=F64)
         scales[3] = torch.tensor([0.5, 0.45, 0.4], dtype=F64)
         special = 3
+    if kind == "generic_camera":   # the same Gaussians seen through projection_cases's generic camera: means in ITS world frame
+        R, t = pc.CAMERAS["generic"]
+        means = pc.to_world(means, R, t)
     return cam, dict(means3D=means, opac=opac, shs=shs, scales=scales, rots=rots), W, H, special
 
 
-def _fd_gradients(cam, inp, deg, wgt, eps=1e-6):
+def _generic_camera_settings(cam, deg):
+    """float64 settings of `cam` behind projection_cases's generic rigid transform: W != I, campos != 0"""
+    view, proj, campos = pc.camera_setup(*pc.CAMERAS["generic"], cam)
+    return rt.RasterSettings(cam.image_height, cam.image_width, math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2), torch.tensor([0.2, 0.5, 0.9], dtype=F64),
+                             1.0, view, proj, deg, campos, False, False)
+
+
+def _fd_gradients(cam, inp, deg, wgt, eps=1e-6, st=None):
     """Central differences of sum(wgt * image) through the float64 C forward, one parameter element at a time."""
-    st = _settings64(cam, deg, torch.tensor([0.2, 0.5, 0.9]))
+    if st is None:
+        st = _settings64(cam, deg, torch.tensor([0.2, 0.5, 0.9]))
 
     def f(v):
         color, _, _ = gs_ref.forward(v["means3D"], v["opac"].reshape(-1), st, shs=v["shs"], scales=v["scales"], rotations=v["rots"])
@@ -206,14 +240,18 @@ def _fd_gradients(cam, inp, deg, wgt, eps=1e-6):
     return out
 
 
-@pytest.mark.parametrize("kind,deg", [("generic", 3), ("generic", 0), ("sh_clamp", 1), ("ewa_clamp", 0), ("alpha_clamp", 0)])
+@pytest.mark.parametrize("kind,deg", [("generic", 3), ("generic", 0), ("sh_clamp", 1), ("ewa_clamp", 0), ("alpha_clamp", 0), ("generic_camera", 3)])
 def test_c_oracle_backward_vs_finite_differences(kind, deg):
     cam, inp, W, H, special = _tiny_scene(kind)
     torch.manual_seed(7)
     wgt = torch.randn(3, H, W, dtype=F64)
-    img, radii, ana = _run("c", cam, inp, deg, F64, wgt)
+    st = None
+    if kind == "generic_camera":   # every entry of W in play, a view direction that is not the mean's: the yardstick of tests/projection_cases.py
+        st = _generic_camera_settings(cam, deg)
+        assert float(st.campos.abs().min()) > 0.1 and float((st.viewmatrix[:3, :3] - torch.eye(3, dtype=F64)).abs().min()) > 0.03
+    img, radii, ana = _run("c", cam, inp, deg, F64, wgt, st=st)
     assert int((radii > 0).sum()) == radii.numel()
-    fd = _fd_gradients(cam, {k: v.clone() for k, v in inp.items()}, deg, wgt)
+    fd = _fd_gradients(cam, {k: v.clone() for k, v in inp.items()}, deg, wgt, st=st)
     scale = {k: float(fd[k].abs().max()) for k in fd}
     assert all(s > 0 for s in scale.values())
 
@@ -225,7 +263,7 @@ def test_c_oracle_backward_vs_finite_differences(kind, deg):
 
     P = radii.numel()
     others = [i for i in range(P) if i != special]
-    if kind in ("generic", "sh_clamp"):
+    if kind in ("generic", "sh_clamp", "generic_camera"):
         # true derivative everywhere (a clamped colour has derivative zero, and the operator masks it to zero)
         for k in ana:
             if k != "means2D":
