@@ -519,6 +519,32 @@ int mi355gs_metrics_rgb8(void* stream, int N, int H, int W, const uint8_t* a, co
                          float* ssim_mean);
 
 /* ----------------------------------------------------------------------------------------------
+ * LPIPS with the VGG16 trunk (csrc/lpips.hip; reference lpipsPyTorch/modules/{lpips,networks,utils}.py as metrics.py:69 calls
+ * it).  a, b: N pairs of interleaved frames, uint8 [N][H][W][3] each, in device memory, any base address.  Per pair:
+ *   x = (byte / 255 - mean) / std in float32, mean (-.030, -.088, -.188), std (.458, .448, .450) — NO rescaling to [-1, 1],
+ *   as the reference feeds `to_tensor` images; five blocks of 2, 2, 3, 3, 3 convolutions (3x3, zero padding 1, bias, ReLU),
+ *   a 2x2 stride-2 max-pool (floor) in front of blocks 2 to 5, block b of width channels[b] (every multiple of 32 from 32 to
+ *   512; the trained net is 64, 128, 256, 512, 512); behind each block's last ReLU a tap:
+ *   n = sqrt(sum_c x_c^2), x^ = x / (n + 1e-10), d = sum_c lin_c (x^_c - y^_c)^2, tap value = mean of d over the block's pixels;
+ *   taps[i][0..4] = the five tap values (taps may be NULL), lpips[i] = their sum.
+ * Exact float32 throughout: every convolution is a k-ordered fused-multiply-add chain (v_mfma_f32_32x32x2_f32; the first layer on
+ * the vector unit), k = (3 ky + kx) Cin + ci, started at 0, the bias added last.  No atomics: equal bits run to run and under
+ * an exchange of a and b; identical frames give exactly 0.
+ * weights: ONE device blob of floats, 16-byte aligned: for each of the 13 convolutions in network order the matrix
+ *   [9 Cin][Cout] (row (3 ky + kx) Cin + ci, i.e. torch's weight.permute(2, 3, 1, 0)) followed by the bias [Cout]; then the five
+ *   lin vectors [channels[b]] (signed values allowed).  Cin of the first convolution is 3.
+ * Launches: 13 convolutions, 4 pools, 5 taps, 1 finish, on the caller's stream; no host synchronisation, no allocation, no
+ * memset.  scratch: the scratch-size query's bytes of device memory, 16-byte aligned, owned by the caller: two activation
+ * buffers of max_b(2 N H_b W_b channels[b]) floats and the taps' partial sums (0 = the sizes are refused).
+ * Limits (MI355GS_EINVAL beyond them, as for null a, b, channels, weights, scratch or lpips and misaligned weights or scratch):
+ * H, W >= 16 (block 5 needs one pixel), N <= 65535, 3 H W <= 2^31 - 1, 2 N H_b W_b channels[b] <= 2^31 - 1 for every block b
+ * (an activation's element index is an int; callers split N), channels[b] a multiple of 32 in [32, 512].
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_lpips_vgg_scratch_bytes(int N, int H, int W, const int channels[5]);
+int mi355gs_lpips_vgg_rgb8(void* stream, int N, int H, int W, const uint8_t* a, const uint8_t* b, const int channels[5],
+                           const float* weights, void* scratch, float* lpips, float* taps);
+
+/* ----------------------------------------------------------------------------------------------
  * PNG files of 8-bit RGB frames, encoded on the device (csrc/png.hip).  frames: uint8 [N][H][W][3] in device memory, any base
  * address (a slice of a stack is fine).  out receives the N files back to back: file i is out[offsets[i] : offsets[i+1]], offsets
  * a device array of N + 1.  Every file is: signature, IHDR (8-bit RGB, no interlace), one IDAT per block of rows_per_block

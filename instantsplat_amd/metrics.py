@@ -6,8 +6,10 @@ mi355gs_metrics_rgb8) on the interleaved bytes the device already holds after `r
 `pose_metrics` is the pose half on the host (numpy).  `evaluate` reads a model directory (or takes the frame stacks
 `pose_tracking.render_test_set` returned) and writes the reference's files.
 
-In: PSNR, SSIM, ATE, RPE_t, RPE_r and the four files.  Out: LPIPS's VGG weights (a caller that has them passes `lpips_fn`),
-reading COLMAP ground-truth poses and the train/test split (dataset conventions: the caller passes `gt_poses`), the plot.
+In: PSNR, SSIM, LPIPS (the VGG16 forward on the device, instantsplat_amd/lpips.py: `evaluate(..., lpips=LpipsVGG(...))`), ATE,
+RPE_t, RPE_r and the four files.  Out: LPIPS's trained weights — they cannot be had offline, the caller loads the two files
+(`LpipsVGG.from_files`) or passes an `lpips_fn` of their own; without either the files lack the LPIPS keys —, reading COLMAP
+ground-truth poses and the train/test split (dataset conventions: the caller passes `gt_poses`), the plot.
 """
 from __future__ import annotations
 
@@ -196,7 +198,7 @@ def _f32_list(values) -> list:
     return torch.tensor(values, dtype=torch.float32).tolist()
 
 
-def evaluate(model_path, gt_poses=None, lpips_fn=None, frames=None) -> dict:
+def evaluate(model_path, gt_poses=None, lpips_fn=None, frames=None, lpips=None) -> dict:
     """reference metrics.py:35-122 for one model directory.  For every test/<method> directory (in sorted order):
       * renders/ and gt/ are read with PIL in SORTED name order (the reference takes os.listdir's order; only the order of the
         lines, of the per-view entries and of the float32 accumulation of the means depends on it), RGB as is, RGBA without its
@@ -204,14 +206,17 @@ def evaluate(model_path, gt_poses=None, lpips_fn=None, frames=None) -> dict:
         frames = {method: [dict(names, renders, gts)]} (what `pose_tracking.render_test_set` returns under "frames"): those
         stacks are scored instead, and no image file is read;
       * test/<method>/metrics.txt: one line per image, `image name{n}, image idx: {i}, PSNR: {p:.2f}, SSIM: {s:.4f}`, with
-        `, LPIPS: {l:.4f}` only if lpips_fn is given;
+        `, LPIPS: {l:.4f}` only if lpips or lpips_fn is given;
       * results.json {method: {SSIM, PSNR[, LPIPS][, RPE_t, RPE_r, ATE]}} and per_view.json {method: {SSIM: {name: value},
         PSNR: {...}[, LPIPS: {...}]}}: the means are float32 means of the float32 per-view values, as the reference takes them.
-        lpips_fn(render [1,3,H,W] float32, gt [1,3,H,W] float32) -> float supplies LPIPS; with lpips_fn=None (the VGG weights
-        cannot be had offline) the files simply lack the "LPIPS" keys;
+        lpips (an `instantsplat_amd.lpips.LpipsVGG`) supplies LPIPS with one `lpips_rgb8` call per group of frames;
+        lpips_fn(render [1,3,H,W] float32, gt [1,3,H,W] float32) -> float supplies it view by view instead (both: ValueError);
+        with neither (the VGG weights cannot be had offline) the files simply lack the "LPIPS" keys;
       * with gt_poses ([n,4,4], the train views' ground truth) the pose half: pose/<method>/pose_optimized.npy against them
         through `pose_metrics`, RPE_t / RPE_r / ATE added to results.json and pose/<method>/pose_eval.txt written.
     Errors propagate (the reference's bare `except` is not reproduced).  -> dict(results=..., per_view=...), the two files' content."""
+    if lpips is not None and lpips_fn is not None:
+        raise ValueError("evaluate takes lpips (an LpipsVGG) or lpips_fn, not both")
     model_path = str(model_path)
     test_dir = os.path.join(model_path, "test")
     methods = sorted(frames) if frames is not None else sorted(os.listdir(test_dir))
@@ -224,13 +229,14 @@ def evaluate(model_path, gt_poses=None, lpips_fn=None, frames=None) -> dict:
             if len(grp["names"]) != int(grp["renders"].shape[0]):
                 raise ValueError(f"{len(grp['names'])} names for {int(grp['renders'].shape[0])} frames")
             m = image_metrics_rgb8(grp["renders"], grp["gts"])
+            lp = lpips.lpips_rgb8(grp["renders"], grp["gts"])["lpips"] if lpips is not None else None
             for k, name in enumerate(grp["names"]):
                 if name in scored:
                     raise ValueError(f"image name {name!r} appears twice")
-                scored[name] = (float(m["psnr"][k]), float(m["ssim"][k]), grp, k)
+                scored[name] = (float(m["psnr"][k]), float(m["ssim"][k]), grp, k, None if lp is None else float(lp[k]))
         names = sorted(scored)
         psnrs, ssims = _f32_list([scored[n][0] for n in names]), _f32_list([scored[n][1] for n in names])
-        lpipss = None
+        lpipss = _f32_list([scored[n][4] for n in names]) if lpips is not None else None
         if lpips_fn is not None:
             to_f32 = lambda t: t.permute(2, 0, 1).contiguous().float().div(255).unsqueeze(0)
             lpipss = _f32_list([float(lpips_fn(to_f32(scored[n][2]["renders"][scored[n][3]]), to_f32(scored[n][2]["gts"][scored[n][3]])))
