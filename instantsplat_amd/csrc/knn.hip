@@ -6,7 +6,8 @@
 // The reference operator sorts points along a Morton curve and prunes 1024-point boxes.  Here: a uniform grid
 // over the bounding box (counting sort of the points by cell: count -> scan -> scatter, 3 launches), then one
 // thread per point walks cubic shells of cells outwards from its own cell and stops as soon as its current
-// third-best distance is no larger than the distance to the shell it has fully covered — exact, O(N) memory,
+// third-best distance is no larger than the distance to the shell it has fully covered (less a margin for the rounding of
+// the cell indices, see k_knn_query) — exact: the three smallest of the computed squared distances, O(N) memory,
 // ~1 ms for 200k points instead of 25 ms for the exhaustive search (which is kept as the fallback for points
 // whose search has not terminated after KNN_MAX_RING shells, e.g. far outliers, and for tiny clouds).
 #include "common.h"
@@ -17,6 +18,7 @@ namespace {
 
 constexpr int KNN_MAX_RING = 6;
 constexpr float KNN_BIG = 3.402823466e38f;
+constexpr float KNN_REACH = 1.0f - 1e-4f;
 
 struct KnnGrid {
   float minx, miny, minz, inv_h, h;
@@ -133,8 +135,10 @@ __global__ __launch_bounds__(256) void k_knn_query(int N, int G, const float* __
         }
       }
     }
-    // every point outside the (2r+1)^3 cube of cells is at least r*h away from q
-    const float reach = (float)r * g.h;
+    // every point outside the (2r+1)^3 cube of cells is at least r*h away from q -- by the cells' real edges.  The indices
+    // are the rounded (x - min) * inv_h, off by up to 3 * 2^-24 * G <= 4.6e-5 of a cell each, so two floats r + 1 cells apart
+    // can be that much closer than r*h: the reach is shrunk by more than twice that (the mirror of the 1.0001 in h)
+    const float reach = (float)r * g.h * KNN_REACH;
     done = b2 <= reach * reach;
   }
   if (!done) {  // far outlier or fewer than 4 points: exhaustive

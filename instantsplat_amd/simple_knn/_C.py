@@ -6,7 +6,7 @@ from .. import _lib
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:
-    pts = _lib.f32c(points)
+    pts = _lib.f32c(points.float() if points.dtype == torch.float64 else points)   # point clouds read from files are float64
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise RuntimeError("points must have dimensions (num_points, 3)")
     dev = _lib.require_device(pts)
