@@ -5,8 +5,8 @@ Everything else in tests/ reaches these kernels through the whole operator and c
 (projection, binning and composite mixed), or switches the composite's own rounding off to judge the projection
 (projection_cases.device_mode).  Here the device runs the raw C ABI (preprocess, the training forward, the backward; precomputed
 colours, identity view, background BG, every byte of `binning` 0 beforehand) at unit levels 0 ... 3, and what the two kernels read
-and leave is read back through the layouts of csrc/common.h, restated below (run_device holds their totals to the library's size
-queries for every frame): the records and lists they read; image, final_T, n_contrib; the quadrant maxima, boundary records and
+and leave is read back through the layouts of csrc/common.h, restated in tests/frame_abi.py (FrameViews holds their totals to the
+library's size queries for every frame): the records and lists they read; image, final_T, n_contrib; the quadrant maxima, boundary records and
 hit masks the forward hands to the backward; the nine moments per Gaussian the backward leaves in the gradient scratch.
 
 THE REFERENCE is replay(): numpy, per tile and pixel, on the device's own records and lists cast to the dtype (projection and sort
@@ -128,7 +128,6 @@ tests/test_composite_emu.py run on it; the first failing test is named, the numb
   (f) `last` not updated for the second hit of a walk step          40: test_forward_per_pixel[needles] (n_contrib; then everything
                                                                      but the case counts)
 """
-import contextlib
 import functools
 import math
 import os
@@ -137,18 +136,17 @@ import re
 import numpy as np
 import torch
 
-from tests import ops_util
+from tests import frame_abi, ops_util
 from tests import tile_length_cases as tl
 from tests.projection_cases import REL
 
 # csrc/composite.hip and csrc/common.h, restated (source_constants() reads the same from the sources)
-GS_TILE = 16
+GS_TILE = frame_abi.GS_TILE
 GS_SEG = tl.GS_SEG
 LEVELS = tuple(range(tl.GS_UNIT_LEVELS))
 ALPHA_MIN = 1.0 / 255.0
 ALPHA_MAX = 0.99
 T_MIN = 1e-4
-REC_BYTES = 48            # GsRec and GsGrad
 
 W, H = 50, 37             # 4 x 3 tiles, a 2-px partial column and a 5-px partial row
 BG = (0.2, 0.5, 0.9)
@@ -182,45 +180,6 @@ def source_constants():
                 ALPHA_MAX=float(one(r"alpha = fminf\(([0-9.]+)f, a1\.w \* gs_exp2\(power2\)\)", src)),
                 ALPHA_MAX_BWD=float(one(r"fmed3f\(av, 0\.0f, ([0-9.]+)f\)", src)),
                 T_MIN=float(one(r"constexpr float T_MIN = ([0-9.]+)f;", src)), FWD_GROUP=int(one(r"constexpr int FWD_GROUP = (\d+);", src)))
-
-
-# ---------------------------------------------------------------------------------------------------- layouts (csrc/common.h)
-def _al(x):
-    return (x + 255) & ~255
-
-
-def _carve(fields):
-    out, o = {}, 0
-    for name, size in fields:
-        out[name] = o
-        o += _al(size)
-    out["total"] = o
-    return out
-
-
-def tiles_layout(W, H):
-    """TilesLayout, restated: byte offsets of the per-tile and per-pixel tables in `tiles`"""
-    gx, gy = (W + GS_TILE - 1) // GS_TILE, (H + GS_TILE - 1) // GS_TILE
-    T, npix = gx * gy, W * H
-    lay = _carve([("count", T * 4), ("cursor", T * 4), ("start", (T + 1) * 4), ("final_T", npix * 4), ("n_contrib", npix * 4), ("order", T * 4),
-                  ("seg_first", (T + 1) * 4), ("part_first", (T + 1) * 4), ("meta", 16), ("qmax", T * 16)])
-    lay.update(gx=gx, gy=gy, T=T)
-    return lay
-
-
-def binning_layout(R, T, min_units, det):
-    """BinningLayout, restated: byte offsets in `binning`, max_units and max_chunks for a capacity of R instances"""
-    n = max(int(R), 1)
-    top = GS_SEG << (tl.GS_UNIT_LEVELS - 1)
-    by_chunks, by_rule, by_top = (n + GS_SEG - 1) // GS_SEG, 2 * min_units + 1, (n + top - 1) // top
-    max_units = max(min(by_chunks, by_rule), by_top) + max(T, 1)
-    max_chunks = by_chunks + 8 * max(T, 1) + 8
-    fields = [("keys", n * 8), ("list", n * 4), ("unit_tile", max_units * 16), ("bstate", max_units * 256 * 16), ("hitmask", max_chunks * 4 * 8)]
-    if det:
-        fields += [("det_rows", n * REC_BYTES), ("det_rowidx", n * 4)]
-    lay = _carve(fields)
-    lay.update(max_units=max_units, max_chunks=max_chunks)
-    return lay
 
 
 # ---------------------------------------------------------------------------------------------------- cases
@@ -324,93 +283,43 @@ def get_case(name):
 
 
 # ---------------------------------------------------------------------------------------------------- the device side
-@contextlib.contextmanager
 def _mode(level, R, det):
     """the unit level (mi355gs_tune_min_units, for a frame of R instances) and the deterministic instantiation, both set before
     the frame's buffers are sized and restored afterwards"""
-    import instantsplat_amd.diff_gaussian_rasterization as dgr
-    was = dgr.set_deterministic(bool(det))
-    try:
-        with tl.at_level(dict(n=R), level):
-            yield
-    finally:
-        dgr.set_deterministic(was)
+    return frame_abi.knobs(min_units=tl.min_units_for(R, level), det=bool(det))
 
 
-def _preprocess(dev, case):
-    from instantsplat_amd import _lib
-    from instantsplat_amd.camera import Camera
-    L = _lib.lib()
-    tanx, tany, _ = _camera()
-    cam = Camera(0, torch.eye(4), math.radians(60), 2 * math.atan(tany), W, H)
-    t = lambda x: x.float().contiguous().to(dev)
-    P = case["P"]
-    a = dict(means=t(case["means"]), q=t(case["q"]), scales=t(case["scales"]), opac=t(case["opac"]), col=t(case["col"]), view=t(torch.eye(4).reshape(-1)),
-             proj=t(cam.projection_matrix.reshape(-1)), campos=t(torch.zeros(3)), bg=t(torch.tensor(BG)), tanx=tanx, tany=tany,
-             geom=torch.zeros(L.mi355gs_raster_geom_bytes(P), dtype=torch.uint8, device=dev),
-             tiles=torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev),
-             radii=torch.zeros(P, dtype=torch.int32, device=dev), nr=torch.zeros(1, dtype=torch.int32, device=dev))
-    p = _lib.ptr
-    _lib.check(L.mi355gs_raster_forward_preprocess(_lib.stream_ptr(dev), P, 0, 0, W, H, p(a["means"]), None, None, p(a["col"]), p(a["opac"]), p(a["scales"]), 1.0,
-                                                   p(a["q"]), None, p(a["view"]), p(a["proj"]), p(a["campos"]), tanx, tany, 0, p(a["radii"]), p(a["geom"]),
-                                                   p(a["tiles"]), p(a["nr"]), None, None, 0), "preprocess")
-    a["R"] = int(a["nr"].item())
-    return a
+def _scene(case):
+    return dict(means=case["means"], rots=case["q"], scales=case["scales"], opac=case["opac"], colors=case["col"])
 
 
 @functools.lru_cache(maxsize=None)
 def _instances(dev, name):
     """the frame's instance count: the unit level is the scan's function of it and of the knob, so it is needed before the frame runs"""
-    return _preprocess(torch.device(dev), get_case(name))["R"]
+    return frame_abi.run_frame(dev, _scene(get_case(name)), frame_abi.identity_camera(W, H), bg=BG, preprocess_only=True).R
 
 
 def run_device(dev, name, level, det=False, dL=None):
     """The case through the raw C ABI at a unit level: preprocess, the training forward and — with a dL/dpixel — the backward.
     Every byte of `binning` is 0 beforehand.  Returns what the composite kernels read and left, as numpy arrays."""
-    from instantsplat_amd import _lib
-    dev = torch.device(dev)
-    L = _lib.lib()
     case = get_case(name)
     P = case["P"]
     R = _instances(str(dev), name)
-    p, stream = _lib.ptr, _lib.stream_ptr(dev)
-    with _lib.on_device(dev), _mode(level, R, det):
-        min_units, det_on = L.mi355gs_tune_min_units(0), L.mi355gs_tune_deterministic(-1)
-        assert bool(det_on) == bool(det)
-        a = _preprocess(dev, case)
-        assert a["R"] == R
-        tlay = tiles_layout(W, H)
-        blay = binning_layout(R, tlay["T"], min_units, det)
-        assert tlay["total"] == L.mi355gs_raster_tiles_bytes(W, H) and blay["total"] == L.mi355gs_raster_binning_bytes(R, W, H), "a layout moved"
-        binning = torch.zeros(blay["total"], dtype=torch.uint8, device=dev)
-        img = torch.zeros(3, H, W, device=dev)
-        _lib.check(L.mi355gs_raster_forward_render(stream, P, W, H, R, p(a["bg"]), p(a["geom"]), p(a["tiles"]), p(binning), p(img), 0), "render")
-        out = dict(name=name, level=level, det=det, R=R, P=P, max_units=blay["max_units"], max_chunks=blay["max_chunks"])
-        if dL is not None:
-            g = torch.from_numpy(np.ascontiguousarray(dL, dtype=np.float32)).to(dev)
-            scratch = torch.zeros(int(L.mi355gs_raster_grad_scratch_bytes(P)), dtype=torch.uint8, device=dev)
-            new = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)
-            d = dict(means3D=new(P, 3), means2D=new(P, 3), colors=new(P, 3), opac=new(P), scales=new(P, 3), rots=new(P, 4))
-            _lib.check(L.mi355gs_raster_backward(stream, P, 0, 0, W, H, p(a["bg"]), p(a["means"]), None, None, p(a["col"]), p(a["opac"]), p(a["scales"]), 1.0,
-                                                 p(a["q"]), None, p(a["view"]), p(a["proj"]), p(a["campos"]), a["tanx"], a["tany"], p(a["geom"]), p(a["tiles"]),
-                                                 p(binning), R, p(a["radii"]), p(img), p(g), p(scratch), p(d["means3D"]), p(d["means2D"]), None, None,
-                                                 p(d["colors"]), p(d["opac"]), p(d["scales"]), p(d["rots"]), None, 0, 0), "backward")
-            out["moments"] = scratch[: P * REC_BYTES].cpu().numpy().view(np.float32).reshape(P, 12)[:, :9].copy()
-            out["dL_dcolors"], out["dL_dopac"] = d["colors"].cpu().numpy(), d["opac"].cpu().numpy()
-    T = tlay["T"]
-    tb, bb = a["tiles"].cpu().numpy(), binning.cpu().numpy()
-    view = lambda buf, off, n, dt: buf[off: off + n * np.dtype(dt).itemsize].view(dt).copy()
-    out["rec"] = a["geom"][: P * REC_BYTES].cpu().numpy().view(np.float32).reshape(P, 12).copy()
-    out["start"] = view(tb, tlay["start"], T + 1, np.uint32).astype(np.int64)
-    out["final_T"] = view(tb, tlay["final_T"], W * H, np.float32).reshape(H, W)
-    out["n_contrib"] = view(tb, tlay["n_contrib"], W * H, np.uint32).astype(np.int64).reshape(H, W)
-    out["seg_first"] = view(tb, tlay["seg_first"], T + 1, np.uint32).astype(np.int64)
-    out["meta"] = view(tb, tlay["meta"], 4, np.uint32).astype(np.int64)
-    out["qmax"] = view(tb, tlay["qmax"], T * 4, np.uint32).astype(np.int64).reshape(T, 4)
-    out["lst"] = view(bb, blay["list"], R, np.uint32).astype(np.int64)
-    out["bstate"] = view(bb, blay["bstate"], blay["max_units"] * 256 * 4, np.float32).reshape(blay["max_units"], 256, 4)
-    out["hitmask"] = view(bb, blay["hitmask"], blay["max_chunks"] * 4, np.uint64).reshape(blay["max_chunks"], 4)
-    out["image"] = img.cpu().numpy()
+    with _mode(level, R, det):
+        assert frame_abi.current_knobs()[1] == int(bool(det))
+        fr = frame_abi.run_frame(dev, _scene(case), frame_abi.identity_camera(W, H), bg=BG, dL=dL)
+    assert fr.R == R
+    v = fr.views
+    out = dict(name=name, level=level, det=det, R=R, P=P, max_units=v.max_units, max_chunks=v.max_chunks)
+    if dL is not None:
+        out["moments"] = fr.moments.cpu().numpy().copy()
+        out["dL_dcolors"], out["dL_dopac"] = fr.grads["colors"].cpu().numpy(), fr.grads["opac"].cpu().numpy()
+    T = v.T
+    out["rec"] = v.np("rec")
+    out["start"], out["seg_first"], out["meta"], out["qmax"] = v.np("tile_start"), v.np("seg_first"), v.np("meta"), v.np("qmax")
+    out["final_T"], out["n_contrib"] = v.np("final_T"), v.np("n_contrib")
+    out["lst"], out["bstate"], out["hitmask"] = v.np("list"), v.np("bstate"), v.np("hitmask")
+    out["image"] = fr.image.cpu().numpy()
     assert out["meta"][2] == 1 << level, (out["meta"], level)
     assert out["start"][0] == 0 and out["start"][T] == R and bool((np.diff(out["start"]) >= 0).all()) and int(out["lst"].max(initial=0)) < P
     return out

@@ -1,8 +1,7 @@
 """Edge cases shared by the CPU (emulated) and GPU tiers."""
-import math
-
 import torch
 
+from tests import frame_abi
 from tests.util import assert_no_worse_than_fp32_oracle, assert_raster_parity, run_custom_case, run_blob_case
 
 
@@ -155,11 +154,7 @@ def check_tile_lists_sorted(dev, n):
     """Exact property of the binning stage, straight through the C ABI: every per-tile list is a duplicate-free set of
     Gaussian indices in ascending (depth bits, index) order — for list lengths on both sides of the sort kernel's
     2048-key register network and 8192-key rank-placement window."""
-    from instantsplat_amd import _lib
-    from instantsplat_amd.camera import Camera
     import numpy as np
-    dev = torch.device(dev)
-    L = _lib.lib()
     g = torch.Generator().manual_seed(11)
     z = 2.0 + 4.0 * torch.rand(n, generator=g)
     z[: n // 50] = z[n // 50: 2 * (n // 50)]   # exact depth ties: the index has to break them
@@ -170,28 +165,9 @@ def check_tile_lists_sorted(dev, n):
     opac = (torch.full((n, 1), 0.02) + 0.02 * torch.rand(n, 1, generator=g)).reshape(-1)
     col = torch.rand(n, 3, generator=g)
     W, H = 48, 32
-    tanx = math.tan(math.radians(60) / 2)
-    tany = tanx * H / W
-    cam = Camera(0, torch.eye(4), math.radians(60), 2 * math.atan(tany), W, H)
-    t = lambda x: x.float().contiguous().to(dev)
-    means, q, scales, opac, col = map(t, (means, q, scales, opac, col))
-    view, proj, campos = t(torch.eye(4).reshape(-1)), t(cam.projection_matrix.reshape(-1)), t(torch.zeros(3))
-    geom = torch.zeros(L.mi355gs_raster_geom_bytes(n), dtype=torch.uint8, device=dev)
-    tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-    radii = torch.zeros(n, dtype=torch.int32, device=dev)
-    nr = torch.zeros(1, dtype=torch.int32, device=dev)
-    p, stream = _lib.ptr, _lib.stream_ptr(dev)
-    _lib.check(L.mi355gs_raster_forward_preprocess(stream, n, 0, 0, W, H, p(means), None, None, p(col), p(opac), p(scales), 1.0, p(q), None,
-                                                   p(view), p(proj), p(campos), tanx, tany, 0, p(radii), p(geom), p(tiles), p(nr), None, None, 0), "preprocess")
-    R = int(nr.item())
-    binning = torch.zeros(L.mi355gs_raster_binning_bytes(R, W, H), dtype=torch.uint8, device=dev)
-    img, bg = torch.zeros(3, H, W, device=dev), torch.zeros(3, device=dev)
-    _lib.check(L.mi355gs_raster_forward_render(stream, n, W, H, R, p(bg), p(geom), p(tiles), p(binning), p(img), 0), "render")
-    T, al = 6, (lambda x: (x + 255) & ~255)
-    # scratch layouts (csrc/common.h): tiles = count | cursor | start[T+1] ...; binning = keys[R] (8 B) | list[R] (4 B) ...
-    start = tiles[2 * al(T * 4): 2 * al(T * 4) + (T + 1) * 4].cpu().view(torch.int32).numpy()
-    lst = binning[al(R * 8): al(R * 8) + R * 4].cpu().view(torch.int32).numpy()
-    depth = geom[: n * 48].cpu().view(torch.float32).reshape(n, 12).numpy()[:, 11]
+    res = frame_abi.run_frame(dev, dict(means=means, rots=q, scales=scales, opac=opac, colors=col), frame_abi.identity_camera(W, H), bg=torch.zeros(3))
+    v, R, T = res.views, res.R, res.views.T
+    start, lst, depth = v.np("tile_start"), v.np("list"), v.np("rec")[:, 11]
     assert start[0] == 0 and start[T] == R and R > 0
     longest = 0
     check_tile_lists_sorted.lengths = [int(start[tile + 1] - start[tile]) for tile in range(T)]
@@ -209,66 +185,34 @@ def check_backward_launch_order(dev, n=3000, min_units=None):
     """The unit table the forward leaves for the backward (csrc/composite.hip, common.h), read raw through the C ABI: it is a
     permutation of every (tile, segment) of the frame; every full-length unit comes before every short one (the tiles' last
     units, which are launched last to shorten the kernel's tail); an entry's slot is seg_first[tile] + segment."""
-    from instantsplat_amd import _lib
-    from instantsplat_amd.camera import Camera
     import numpy as np
-    dev = torch.device(dev)
-    L = _lib.lib()
-    old = L.mi355gs_tune_min_units(0)
-    if min_units is not None:
-        L.mi355gs_tune_min_units(min_units)
-    try:
-        g = torch.Generator().manual_seed(3)
-        z = 2.0 + 4.0 * torch.rand(n, generator=g)
-        means = torch.stack([0.5 * (2 * torch.rand(n, generator=g) - 1) * z, 0.35 * (2 * torch.rand(n, generator=g) - 1) * z, z], dim=1)
-        q = torch.randn(n, 4, generator=g)
-        q = q / q.norm(dim=1, keepdim=True)
-        scales = 0.02 + 0.05 * torch.rand(n, 3, generator=g)
-        opac = torch.full((n,), 0.05) + 0.1 * torch.rand(n, generator=g)
-        col = torch.rand(n, 3, generator=g)
-        W, H = 80, 48
-        tanx = math.tan(math.radians(60) / 2)
-        tany = tanx * H / W
-        cam = Camera(0, torch.eye(4), math.radians(60), 2 * math.atan(tany), W, H)
-        t = lambda x: x.float().contiguous().to(dev)
-        means, q, scales, opac, col = map(t, (means, q, scales, opac, col))
-        view, proj, campos = t(torch.eye(4).reshape(-1)), t(cam.projection_matrix.reshape(-1)), t(torch.zeros(3))
-        geom = torch.zeros(L.mi355gs_raster_geom_bytes(n), dtype=torch.uint8, device=dev)
-        tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-        radii = torch.zeros(n, dtype=torch.int32, device=dev)
-        nr = torch.zeros(1, dtype=torch.int32, device=dev)
-        p, stream = _lib.ptr, _lib.stream_ptr(dev)
-        _lib.check(L.mi355gs_raster_forward_preprocess(stream, n, 0, 0, W, H, p(means), None, None, p(col), p(opac), p(scales), 1.0, p(q), None,
-                                                       p(view), p(proj), p(campos), tanx, tany, 0, p(radii), p(geom), p(tiles), p(nr), None, None, 0), "preprocess")
-        R = int(nr.item())
-        binning = torch.zeros(L.mi355gs_raster_binning_bytes(R, W, H), dtype=torch.uint8, device=dev)
-        img, bg = torch.zeros(3, H, W, device=dev), torch.zeros(3, device=dev)
-        _lib.check(L.mi355gs_raster_forward_render(stream, n, W, H, R, p(bg), p(geom), p(tiles), p(binning), p(img), 0), "render")
-        gx, gy = (W + 15) // 16, (H + 15) // 16
-        T, al = gx * gy, (lambda x: (x + 255) & ~255)
-        # scratch layouts (csrc/common.h).  tiles = count | cursor | start[T+1] | final_T | n_contrib | order | seg_first[T+1] |
-        # part_first[T+1] | meta; binning = keys[R] (8 B) | list[R] (4 B) | unit table (16 B per entry) | boundary records
-        tb = tiles.cpu().numpy()
-        o = 2 * al(T * 4)
-        start = tb[o: o + (T + 1) * 4].view(np.int32); o += al((T + 1) * 4) + 2 * al(W * H * 4) + al(T * 4)
-        seg_first = tb[o: o + (T + 1) * 4].view(np.int32); o += al((T + 1) * 4)
-        part_first = tb[o: o + (T + 1) * 4].view(np.int32); o += al((T + 1) * 4)
-        meta = tb[o: o + 16].view(np.int32)
-        n_units, chunks, n_short = int(meta[1]), int(meta[2]), int(meta[3])
-        seg_len = 64 * chunks
-        count = np.diff(start)
-        assert n_units == int(np.sum((count + seg_len - 1) // seg_len)) == int(seg_first[T]) and n_short == int(np.sum(count % seg_len != 0))
-        table = binning.cpu().numpy()[al(R * 8) + al(R * 4):][: n_units * 16].view(np.uint32).reshape(n_units, 4)
-        where, seg, slot = table[:, 0], table[:, 1], table[:, 2]
-        tile = (where >> 16) * gx + (where & 0xFFFF)
-        assert bool((tile < T).all()) and bool((slot == seg_first[tile] + seg).all())
-        assert len(np.unique(slot)) == n_units and int(slot.max()) == n_units - 1          # every unit exactly once
-        last_seg = (count[tile] + seg_len - 1) // seg_len - 1
-        short = (seg == last_seg) & (count[tile] % seg_len != 0)
-        assert int(short.sum()) == n_short and not short[: n_units - n_short].any() and short[n_units - n_short:].all()
-        return n_units, n_short, chunks
-    finally:
-        L.mi355gs_tune_min_units(old)
+    g = torch.Generator().manual_seed(3)
+    z = 2.0 + 4.0 * torch.rand(n, generator=g)
+    means = torch.stack([0.5 * (2 * torch.rand(n, generator=g) - 1) * z, 0.35 * (2 * torch.rand(n, generator=g) - 1) * z, z], dim=1)
+    q = torch.randn(n, 4, generator=g)
+    q = q / q.norm(dim=1, keepdim=True)
+    scales = 0.02 + 0.05 * torch.rand(n, 3, generator=g)
+    opac = torch.full((n,), 0.05) + 0.1 * torch.rand(n, generator=g)
+    col = torch.rand(n, 3, generator=g)
+    W, H = 80, 48
+    with frame_abi.knobs(min_units=min_units):
+        v = frame_abi.run_frame(dev, dict(means=means, rots=q, scales=scales, opac=opac, colors=col), frame_abi.identity_camera(W, H), bg=torch.zeros(3)).views
+    gx, T = v.gx, v.T
+    start, seg_first, meta = v.np("tile_start"), v.np("seg_first"), v.np("meta")
+    n_units, chunks, n_short = int(meta[1]), int(meta[2]), int(meta[3])
+    seg_len = 64 * chunks
+    count = np.diff(start)
+    assert n_units == int(np.sum((count + seg_len - 1) // seg_len)) == int(seg_first[T]) and n_short == int(np.sum(count % seg_len != 0))
+    assert n_units <= v.max_units
+    table = v.np("unit_tile")[:n_units]      # uint4 per unit, in launch order: (tile x | tile y << 16, segment, slot, 0)
+    where, seg, slot = table[:, 0], table[:, 1], table[:, 2]
+    tile = (where >> 16) * gx + (where & 0xFFFF)
+    assert bool((tile < T).all()) and bool((slot == seg_first[tile] + seg).all())
+    assert len(np.unique(slot)) == n_units and int(slot.max()) == n_units - 1          # every unit exactly once
+    last_seg = (count[tile] + seg_len - 1) // seg_len - 1
+    short = (seg == last_seg) & (count[tile] % seg_len != 0)
+    assert int(short.sum()) == n_short and not short[: n_units - n_short].any() and short[n_units - n_short:].all()
+    return n_units, n_short, chunks
 
 
 def check_operator_error_behaviour(dev, tmp_path):
@@ -328,13 +272,8 @@ def check_tile_lists_against_oracle(dev, n, W=80, H=48, seed=5, scale_boost=1.0,
       * every instance the device dropped has alpha < 1/255 at every pixel of that tile — it could not have been blended,
         so image, n_contrib-as-a-set and all gradients are unaffected by dropping it;
       * no instance is dropped that reaches alpha >= 1/255 anywhere (the same statement, from the other side)."""
-    from instantsplat_amd import _lib
-    from instantsplat_amd.camera import Camera
     from oracle import gs_ref
     from oracle.raster_torch import RasterSettings
-    import numpy as np
-    dev = torch.device(dev)
-    L = _lib.lib()
     g = torch.Generator().manual_seed(seed)
     z = 2.0 + 4.0 * torch.rand(n, generator=g)
     means = torch.stack([0.6 * (2 * torch.rand(n, generator=g) - 1) * z, 0.4 * (2 * torch.rand(n, generator=g) - 1) * z, z], dim=1)
@@ -345,68 +284,22 @@ def check_tile_lists_against_oracle(dev, n, W=80, H=48, seed=5, scale_boost=1.0,
     scales = (0.01 + 0.08 * torch.rand(n, 3, generator=g) ** 2) * scale_boost
     opac = 0.005 + 0.9 * torch.rand(n, generator=g) ** 3
     col = torch.rand(n, 3, generator=g)
-    tanx = math.tan(math.radians(60) / 2)
-    tany = tanx * H / W
-    cam = Camera(0, torch.eye(4), math.radians(60), 2 * math.atan(tany), W, H)
-    t = lambda x: x.float().contiguous().to(dev)
-    d_means, d_q, d_scales, d_opac, d_col = map(t, (means, q, scales, opac, col))
-    view, proj, campos = t(torch.eye(4).reshape(-1)), t(cam.projection_matrix.reshape(-1)), t(torch.zeros(3))
-    geom = torch.zeros(L.mi355gs_raster_geom_bytes(n), dtype=torch.uint8, device=dev)
-    tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-    radii = torch.zeros(n, dtype=torch.int32, device=dev)
-    nr = torch.zeros(1, dtype=torch.int32, device=dev)
-    p, stream = _lib.ptr, _lib.stream_ptr(dev)
-    _lib.check(L.mi355gs_raster_forward_preprocess(stream, n, 0, 0, W, H, p(d_means), None, None, p(d_col), p(d_opac), p(d_scales), 1.0,
-                                                   p(d_q), None, p(view), p(proj), p(campos), tanx, tany, 0, p(radii), p(geom), p(tiles),
-                                                   p(nr), None, None, 0), "preprocess")
-    R = int(nr.item())
-    binning = torch.zeros(L.mi355gs_raster_binning_bytes(R, W, H), dtype=torch.uint8, device=dev)
-    img, bg = torch.zeros(3, H, W, device=dev), torch.zeros(3, device=dev)
-    _lib.check(L.mi355gs_raster_forward_render(stream, n, W, H, R, p(bg), p(geom), p(tiles), p(binning), p(img), 0), "render")
-    gx, gy = (W + 15) // 16, (H + 15) // 16
-    T, al = gx * gy, (lambda x: (x + 255) & ~255)
-    start = tiles[2 * al(T * 4): 2 * al(T * 4) + (T + 1) * 4].cpu().view(torch.int32).numpy()
-    lst = binning[al(R * 8): al(R * 8) + R * 4].cpu().view(torch.int32).numpy()
-    rec = geom[: n * 48].cpu().view(torch.float32).reshape(n, 12).numpy().astype(np.float64)
+    cam = frame_abi.identity_camera(W, H)
+    res = frame_abi.run_frame(dev, dict(means=means, rots=q, scales=scales, opac=opac, colors=col), cam, bg=torch.zeros(3))
+    v, R = res.views, res.R
     if entry_counts is not None:
         # what the count kernel handed the scatter kernel (common.h GeomLayout): per 512-Gaussian workgroup, the number of
         # touched tiles it listed, or ~0 = "more than the list holds, count again"
-        chunks = (n + 511) // 512
-        off = al(n * 48) + al(n * 24) + al(n * 8) + al(n) + al(n * 4) + al(chunks * 1024 * 4)
-        entry_counts.extend(int(v) for v in geom[off: off + chunks * 4].cpu().view(torch.int32).numpy().astype(np.int64) & 0xffffffff)
+        entry_counts.extend(int(x) for x in v.np("bin_n"))
 
-    settings = RasterSettings(image_height=H, image_width=W, tanfovx=tanx, tanfovy=tany, bg=torch.zeros(3), scale_modifier=1.0,
-                              viewmatrix=torch.eye(4), projmatrix=cam.projection_matrix.cpu(), sh_degree=0, campos=torch.zeros(3),
+    settings = RasterSettings(image_height=H, image_width=W, tanfovx=cam["tanx"], tanfovy=cam["tany"], bg=torch.zeros(3), scale_modifier=1.0,
+                              viewmatrix=torch.eye(4), projmatrix=cam["proj"].cpu(), sh_degree=0, campos=torch.zeros(3),
                               prefiltered=False, debug=False)
     _, radii_ref, ctx = gs_ref.forward(means, opac, settings, colors_precomp=col, scales=scales, rotations=q)
-    aux = ctx.aux(W, H)
-    o_start, o_list = aux["tile_start"].numpy(), aux["list"].numpy()
     R_ref = ctx.num_rendered
-    assert start[0] == 0 and start[T] == R and 0 < R <= R_ref
-    dropped = kept = 0
-    worst = 0.0
-    for tile in range(T):
-        mine = lst[start[tile]:start[tile + 1]]
-        theirs = o_list[o_start[tile]:o_start[tile + 1]]
-        in_mine = np.isin(theirs, mine)
-        assert len(np.unique(mine)) == len(mine) and bool(np.isin(mine, theirs).all()), tile       # subset of the reference's list
-        assert bool((theirs[in_mine] == mine).all()), tile                                          # same relative order
-        gone = theirs[~in_mine]
-        kept += len(mine)
-        dropped += len(gone)
-        if len(gone) == 0:
-            continue
-        tx, ty = tile % gx, tile // gx
-        xs = np.arange(tx * 16, min(tx * 16 + 16, W), dtype=np.float64)
-        ys = np.arange(ty * 16, min(ty * 16 + 16, H), dtype=np.float64)
-        r = rec[gone]   # x, y, hx, hy | A, C, B (log2-scaled conic), opacity | r, g, b, depth
-        dx = r[:, 0, None, None] - xs[None, None, :]
-        dy = r[:, 1, None, None] - ys[None, :, None]
-        power2 = r[:, 4, None, None] * dx * dx + r[:, 5, None, None] * dy * dy + r[:, 6, None, None] * dx * dy
-        alpha = r[:, 7, None, None] * np.exp2(np.minimum(power2, 0.0))
-        alpha = np.where(power2 > 0, 0.0, alpha)
-        worst = max(worst, float(alpha.max()))
-        assert float(alpha.max()) < 1.0 / 255.0, (tile, float(alpha.max()))
+    start = v.np("tile_start")
+    assert start[0] == 0 and start[v.T] == R and 0 < R <= R_ref
+    kept, dropped, worst = frame_abi.lists_against_oracle(v, ctx.aux(W, H), W, H)
     assert kept == R and kept + dropped == R_ref
     return R, R_ref, worst
 

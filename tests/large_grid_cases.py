@@ -8,6 +8,7 @@ import re
 import numpy as np
 import torch
 
+from tests import frame_abi
 from tests.util import assert_raster_parity, run_blob_case
 
 # The thresholds of csrc/binning.hip, restated (test_large_grid_emu.py::test_thresholds_are_the_sources holds them to the source:
@@ -73,12 +74,8 @@ def check_tile_lists(dev, n, W, H, seed=5, sigma_max_px=20.0, first_chunk_tiny=T
     Returns what the caller needs to show which paths ran: R, R_ref, worst (largest alpha of a dropped instance), count
     (instances per tile), area (tiles in each Gaussian's device rectangle), rect0 (Gaussian 0's), entry_n (per binning workgroup;
     LDS forms only)."""
-    from instantsplat_amd import _lib
-    from instantsplat_amd.camera import Camera
     from oracle import gs_ref
     from oracle.raster_torch import RasterSettings
-    dev = torch.device(dev)
-    L = _lib.lib()
     g = torch.Generator().manual_seed(seed)
     tanx = math.tan(math.radians(60) / 2)
     tany = tanx * H / W
@@ -101,74 +98,25 @@ def check_tile_lists(dev, n, W, H, seed=5, sigma_max_px=20.0, first_chunk_tiny=T
         means[:m, 0], means[:m, 1] = corner[:, 0] * tanx * z[:m], corner[:, 1] * tany * z[:m]
     scales = sigma_px * z[:, None] / focal
     col = torch.rand(n, 3, generator=g)
-    cam = Camera(0, torch.eye(4), math.radians(60), 2 * math.atan(tany), W, H)
-    t = lambda x: x.float().contiguous().to(dev)
-    d_means, d_q, d_scales, d_opac, d_col = map(t, (means, q, scales, opac, col))
-    view, proj, campos = t(torch.eye(4).reshape(-1)), t(cam.projection_matrix.reshape(-1)), t(torch.zeros(3))
-    geom = torch.zeros(L.mi355gs_raster_geom_bytes(n), dtype=torch.uint8, device=dev)
-    tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-    radii = torch.zeros(n, dtype=torch.int32, device=dev)
-    nr = torch.zeros(1, dtype=torch.int32, device=dev)
-    p, stream = _lib.ptr, _lib.stream_ptr(dev)
-    _lib.check(L.mi355gs_raster_forward_preprocess(stream, n, 0, 0, W, H, p(d_means), None, None, p(d_col), p(d_opac), p(d_scales), 1.0,
-                                                   p(d_q), None, p(view), p(proj), p(campos), tanx, tany, 0, p(radii), p(geom), p(tiles),
-                                                   p(nr), None, None, 0), "preprocess")
-    R = int(nr.item())
-    binning = torch.zeros(L.mi355gs_raster_binning_bytes(R, W, H), dtype=torch.uint8, device=dev)
-    img, bg = torch.zeros(3, H, W, device=dev), torch.zeros(3, device=dev)
-    _lib.check(L.mi355gs_raster_forward_render(stream, n, W, H, R, p(bg), p(geom), p(tiles), p(binning), p(img), 0), "render")
-    al = lambda x: (x + 255) & ~255
-    # scratch layouts (csrc/common.h): tiles = count | cursor | start[T+1] ...; binning = keys[R] (8 B) | list[R] (4 B) ...;
-    # geom = records (48 B) | cov3D (24 B) | rect (8 B) | clamped (1 B) | depth (4 B) | entries | entry_n
-    start = tiles[2 * al(T * 4): 2 * al(T * 4) + (T + 1) * 4].cpu().view(torch.int32).numpy()
-    lst = binning[al(R * 8): al(R * 8) + R * 4].cpu().view(torch.int32).numpy()
-    rec = geom[: n * 48].cpu().view(torch.float32).reshape(n, 12).numpy().astype(np.float64)
-    o_rect = al(n * 48) + al(n * 24)
-    rect = geom[o_rect: o_rect + n * 8].cpu().view(torch.int32).numpy().astype(np.int64).reshape(n, 2)
+    cam = frame_abi.identity_camera(W, H)
+    res = frame_abi.run_frame(dev, dict(means=means, rots=q, scales=scales, opac=opac, colors=col), cam, bg=torch.zeros(3))
+    v, R = res.views, res.R
+    start, rect = v.np("tile_start"), v.np("rect")
     x0, y0, x1, y1 = rect[:, 0] & 0xffff, (rect[:, 0] >> 16) & 0xffff, rect[:, 1] & 0xffff, (rect[:, 1] >> 16) & 0xffff
     area = np.where((x1 > x0) & (y1 > y0), (x1 - x0) * (y1 - y0), 0)
-    chunks = (n + BIN_CHUNK - 1) // BIN_CHUNK
-    o_n = o_rect + al(n * 8) + al(n) + al(n * 4) + al(chunks * BIN_ENTRIES * 4)
-    entry_n = [int(v) for v in geom[o_n: o_n + chunks * 4].cpu().view(torch.int32).numpy().astype(np.int64) & 0xffffffff]
+    entry_n = [int(x) for x in v.np("bin_n")]
 
     settings = RasterSettings(image_height=H, image_width=W, tanfovx=tanx, tanfovy=tany, bg=torch.zeros(3), scale_modifier=1.0,
-                              viewmatrix=torch.eye(4), projmatrix=cam.projection_matrix.cpu(), sh_degree=0, campos=torch.zeros(3),
+                              viewmatrix=torch.eye(4), projmatrix=cam["proj"].cpu(), sh_degree=0, campos=torch.zeros(3),
                               prefiltered=False, debug=False)
     _, _, ctx = gs_ref.forward(means, opac, settings, colors_precomp=col, scales=scales, rotations=q)
-    aux = ctx.aux(W, H)
-    o_start, o_list = aux["tile_start"].numpy(), aux["list"].numpy()
     R_ref = ctx.num_rendered
     assert start[0] == 0 and start[T] == R and 0 < R <= R_ref
     assert int(area.sum()) == R                                  # every instance of every device rectangle is in a list
-    assert bool((np.diff(start.astype(np.int64)) >= 0).all())
-    dropped = kept = 0
-    worst = 0.0
-    for tile in range(T):
-        mine = lst[start[tile]:start[tile + 1]]
-        theirs = o_list[o_start[tile]:o_start[tile + 1]]
-        if len(mine) == 0 and len(theirs) == 0:
-            continue
-        in_mine = np.isin(theirs, mine)
-        assert len(np.unique(mine)) == len(mine) and bool(np.isin(mine, theirs).all()), tile       # subset of the reference's list
-        assert bool((theirs[in_mine] == mine).all()), tile                                          # same relative order
-        gone = theirs[~in_mine]
-        kept += len(mine)
-        dropped += len(gone)
-        if len(gone) == 0:
-            continue
-        tx, ty = tile % gx, tile // gx
-        xs = np.arange(tx * 16, min(tx * 16 + 16, W), dtype=np.float64)
-        ys = np.arange(ty * 16, min(ty * 16 + 16, H), dtype=np.float64)
-        r = rec[gone]   # x, y, hx, hy | A, C, B (log2-scaled conic), opacity | r, g, b, depth
-        dx = r[:, 0, None, None] - xs[None, None, :]
-        dy = r[:, 1, None, None] - ys[None, :, None]
-        power2 = r[:, 4, None, None] * dx * dx + r[:, 5, None, None] * dy * dy + r[:, 6, None, None] * dx * dy
-        alpha = r[:, 7, None, None] * np.exp2(np.minimum(power2, 0.0))
-        alpha = np.where(power2 > 0, 0.0, alpha)
-        worst = max(worst, float(alpha.max()))
-        assert float(alpha.max()) < 1.0 / 255.0, (tile, float(alpha.max()))
+    assert bool((np.diff(start) >= 0).all())
+    kept, dropped, worst = frame_abi.lists_against_oracle(v, ctx.aux(W, H), W, H)
     assert kept == R and kept + dropped == R_ref
-    return dict(R=R, R_ref=R_ref, worst=worst, count=np.diff(start.astype(np.int64)), area=area, entry_n=entry_n,
+    return dict(R=R, R_ref=R_ref, worst=worst, count=np.diff(start), area=area, entry_n=entry_n,
                 rect0=(int(x0[0]), int(y0[0]), int(x1[0]), int(y1[0])))
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from oracle import knn_ref, ssim_ref
+from tests import frame_abi
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_vectors.npz"))
 T = lambda k: torch.from_numpy(G[k])
@@ -1509,26 +1510,22 @@ def check_render_only_forward(dev, Wm=20, W=80, H=48):
                 pkg = render(cam, g, st.pipe, st.background, camera_pose=pose)
             stats = dgr.last_frame_stats()
             lf = dgr._LAST_FRAME
+            v = frame_abi.FrameViews.of_last_frame(lf)
+            assert v.render_only == no_grad
             return (pkg["render"].detach().cpu().clone(), pkg["radii"].cpu().clone(), stats, int(lf["binning"].numel()), int(lf["capacity"]),
-                    lf["tiles"].cpu().clone())
+                    (v.final_T.view(torch.int32).cpu().clone(), v.n_contrib.cpu().clone()))
         finally:
             dgr.keep_last_frame(False)
 
-    img_t, rad_t, stats_t, bytes_t, cap_t, tiles_t = frame(no_grad=False)
-    img_r, rad_r, stats_r, bytes_r, cap_r, tiles_r = frame(no_grad=True)
+    img_t, rad_t, stats_t, bytes_t, cap_t, state_t = frame(no_grad=False)
+    img_r, rad_r, stats_r, bytes_r, cap_r, state_r = frame(no_grad=True)
     assert cap_t == cap_r and stats_t == stats_r and stats_t[0] > 0
     assert bytes_t == int(L.mi355gs_raster_binning_bytes(cap_t, W, H))
     assert bytes_r == max(int(L.mi355gs_raster_binning_bytes_render_only(cap_r, W, H)), 1) < bytes_t
     assert torch.equal(img_t, img_r) and torch.equal(rad_t, rad_r)
-    # the per-pixel state the two instantiations share (final_T, n_contrib: include/mi355gs.h `tiles`) — the words in front of
-    # the backward-only tables are the same bits
-    npix_words = W * H
-    nt = ((W + 15) // 16) * ((H + 15) // 16)
-    al = lambda n: (n + 255) // 256 * 256
-    off_final_T = 2 * al(nt * 4) + al((nt + 1) * 4)   # behind count, cursor and start (csrc/common.h TilesLayout)
-    a = tiles_t[off_final_T: off_final_T + 8 * npix_words]
-    b = tiles_r[off_final_T: off_final_T + 8 * npix_words]
-    assert torch.equal(a, b)
+    # the per-pixel state the two instantiations share (include/mi355gs.h `tiles`): final_T and n_contrib, each in full, are the
+    # same bits
+    assert torch.equal(state_t[0], state_r[0]) and torch.equal(state_t[1], state_r[1])
     # render() on the compiled binding, under no_grad and with requires_grad inputs
     ext = _lib.compiled()
     if ext is not None:

@@ -75,7 +75,7 @@ from instantsplat_amd.camera import Camera
 from instantsplat_amd.synthetic import syn_blob
 from oracle import gs_ref, pose_ref
 from oracle import raster_torch as rt
-from tests import ops_util
+from tests import frame_abi, ops_util
 from tests.pose_adam_util import LIMITS, judge_components
 
 F64, F32 = torch.float64, torch.float32
@@ -531,35 +531,24 @@ def judge_rows(case, what, tensor, dev, r32, r64, index=None, path="operator"):
 
 
 # ---------------------------------------------------------------------------------------------------- check 1: forward records
-def _align(x):
-    return (x + 255) & ~255
+def _scene(case, split_sh=False):
+    i = case.inp
+    sc = dict(means=i["means3D"], opac=i["opac"], colors=i.get("colors"), scales=i.get("scales"), rots=i.get("rots"), cov3D=i.get("cov3D"), mod=case.mod)
+    shs = i.get("shs")
+    sc.update(dict(shs=shs[:, :1], shs_rest=shs[:, 1:]) if split_sh else dict(shs=shs))
+    return sc
+
+
+def _camera(case):
+    return dict(W=case.W, H=case.H, view=case.view, proj=case.proj, campos=case.campos, tanx=case.tanx, tany=case.tany)
 
 
 def device_preprocess(dev, case):
     """mi355gs_raster_forward_preprocess alone -> (GsRec rows [P,12] float64, radii, clamp bytes): csrc/common.h GsRec is
-    x, y, hx, hy | -a/2 log2e, -c/2 log2e, -b log2e, opacity | r, g, b, depth; GeomLayout puts the clamp bytes behind the
-    records, the 3-D covariances and the tile rectangles"""
-    from instantsplat_amd import _lib
-    dev = torch.device(dev)
-    L = _lib.lib()
-    P, W, H = case.P, case.W, case.H
-    t = lambda x: None if x is None else x.float().contiguous().to(dev)
-    i = case.inp
-    means, opac, shs, col, scales, rots, cov = (t(i.get(k)) for k in ("means3D", "opac", "shs", "colors", "scales", "rots", "cov3D"))
-    view, proj, campos = t(case.view.reshape(-1)), t(case.proj.reshape(-1)), t(case.campos)
-    geom = torch.zeros(L.mi355gs_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
-    tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-    radii = torch.full((P,), -7, dtype=torch.int32, device=dev)    # every radius is written, 0 for a culled Gaussian
-    nr = torch.zeros(1, dtype=torch.int32, device=dev)
-    p = _lib.ptr
-    M = 0 if shs is None else shs.shape[1]
-    with _lib.on_device(dev):
-        _lib.check(L.mi355gs_raster_forward_preprocess(_lib.stream_ptr(dev), P, case.deg, M, W, H, p(means), p(shs), None, p(col), p(opac.reshape(-1)),
-                                                       p(scales), float(case.mod), p(rots), p(cov), p(view), p(proj), p(campos), case.tanx, case.tany, 0,
-                                                       p(radii), p(geom), p(tiles), p(nr), None, None, 0), "preprocess")
-    rec = geom[: P * 48].cpu().view(torch.float32).reshape(P, 12).double()
-    off = _align(P * 48) + _align(P * 24) + _align(P * 8)
-    return rec, radii.cpu(), geom[off: off + P].cpu().to(torch.int64)
+    x, y, hx, hy | -a/2 log2e, -c/2 log2e, -b log2e, opacity | r, g, b, depth.  The radii are pre-filled with -7: every radius is
+    written, 0 for a culled Gaussian."""
+    res = frame_abi.run_frame(dev, _scene(case), _camera(case), bg=case.bg, sh=case.deg, radii_fill=-7, preprocess_only=True)
+    return res.views.rec.cpu().double(), res.radii.cpu(), res.views.clamped.cpu().to(torch.int64)
 
 
 def check_forward_records(dev, name):
@@ -590,7 +579,6 @@ def check_forward_records(dev, name):
 
 
 # ---------------------------------------------------------------------------------------------------- check 2: gradients per row
-@contextlib.contextmanager
 def device_mode(case):
     """How the device runs a case whose gradients are judged row by row: the case's dL/dscale convention, and two settings that
     keep csrc/composite.hip's own rounding out of a comparison that is about the per-Gaussian kernels.
@@ -604,18 +592,7 @@ def device_mode(case):
       * The deterministic backward: the order of the float atomics differs between any two runs on the GPU, which moved the
         worst row of a tensor by tens of per cent from run to run (blob/translation/sh1, grad scales: under and over its limit in
         two runs of the same build) — a maximum over rows judged against a limit has to be the same number every time."""
-    from instantsplat_amd import _lib
-    import instantsplat_amd.diff_gaussian_rasterization as dgr
-    L = _lib.lib()
-    old_scale, old_units = L.mi355gs_tune_scale_grad(int(case.exact)), L.mi355gs_tune_min_units(0)
-    L.mi355gs_tune_min_units(1)
-    was = dgr.set_deterministic(True)
-    try:
-        yield
-    finally:
-        dgr.set_deterministic(was)
-        L.mi355gs_tune_min_units(old_units)
-        L.mi355gs_tune_scale_grad(old_scale)
+    return frame_abi.knobs(min_units=1, det=True, scale_grad=int(case.exact))
 
 
 def run_operator(dev, case):
@@ -632,37 +609,11 @@ def run_operator(dev, case):
 
 def run_split_abi(dev, case):
     """the case through the raw C ABI with split SH storage: shs = the DC coefficient [P,1,3], shs_rest = the other 15"""
-    from instantsplat_amd import _lib
-    dev = torch.device(dev)
-    L = _lib.lib()
-    P, W, H = case.P, case.W, case.H
-    t = lambda x: x.float().contiguous().to(dev)
-    i = case.inp
-    means, opac, scales, rots = t(i["means3D"]), t(i["opac"].reshape(-1)), t(i["scales"]), t(i["rots"])
-    f_dc, f_rest = t(i["shs"][:, :1]), t(i["shs"][:, 1:])
-    view, proj, campos, bg, wgt = t(case.view.reshape(-1)), t(case.proj.reshape(-1)), t(case.campos), t(case.bg), t(case.wgt)
-    geom = torch.zeros(L.mi355gs_raster_geom_bytes(P), dtype=torch.uint8, device=dev)
-    tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-    radii = torch.zeros(P, dtype=torch.int32, device=dev)
-    nr = torch.zeros(1, dtype=torch.int32, device=dev)
-    p, stream = _lib.ptr, _lib.stream_ptr(dev)
-    new = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=dev)     # every output row must be written
-    d = dict(means3D=new(P, 3), means2D=new(P, 3), dc=new(P, 1, 3), rest=new(P, 15, 3), colors=new(P, 3), opac=new(P), scales=new(P, 3), rots=new(P, 4))
-    with _lib.on_device(dev), device_mode(case):
-        _lib.check(L.mi355gs_raster_forward_preprocess(stream, P, case.deg, 16, W, H, p(means), p(f_dc), p(f_rest), None, p(opac), p(scales), float(case.mod),
-                                                       p(rots), None, p(view), p(proj), p(campos), case.tanx, case.tany, 0, p(radii), p(geom), p(tiles),
-                                                       p(nr), None, None, 0), "preprocess")
-        R = int(nr.item())
-        binning = torch.zeros(max(int(L.mi355gs_raster_binning_bytes(R, W, H)), 1), dtype=torch.uint8, device=dev)
-        img = torch.zeros(3, H, W, device=dev)
-        _lib.check(L.mi355gs_raster_forward_render(stream, P, W, H, R, p(bg), p(geom), p(tiles), p(binning), p(img), 0), "render")
-        scratch = torch.zeros(int(L.mi355gs_raster_grad_scratch_bytes(P)), dtype=torch.uint8, device=dev)
-        _lib.check(L.mi355gs_raster_backward(stream, P, case.deg, 16, W, H, p(bg), p(means), p(f_dc), p(f_rest), None, p(opac), p(scales), float(case.mod),
-                                             p(rots), None, p(view), p(proj), p(campos), case.tanx, case.tany, p(geom), p(tiles), p(binning), R, p(radii),
-                                             p(img), p(wgt), p(scratch), p(d["means3D"]), p(d["means2D"]), p(d["dc"]), p(d["rest"]), p(d["colors"]),
-                                             p(d["opac"]), p(d["scales"]), p(d["rots"]), None, 0, 0), "backward")
-    grads = dict(means3D=d["means3D"], means2D=d["means2D"], opac=d["opac"].reshape(P, 1), shs=torch.cat([d["dc"], d["rest"]], 1), scales=d["scales"], rots=d["rots"])
-    return dict(color=img.cpu(), radii=radii.cpu(), grads={k: v.cpu() for k, v in grads.items()})
+    with device_mode(case):
+        res = frame_abi.run_frame(dev, _scene(case, split_sh=True), _camera(case), bg=case.bg, sh=case.deg, dL=case.wgt)
+    d, P = res.grads, case.P
+    grads = dict(means3D=d["means3D"], means2D=d["means2D"], opac=d["opac"].reshape(P, 1), shs=torch.cat([d["shs"], d["shs_rest"]], 1), scales=d["scales"], rots=d["rots"])
+    return dict(color=res.image.cpu(), radii=res.radii.cpu(), grads={k: v.cpu() for k, v in grads.items()})
 
 
 def check_gradient_rows(dev, name, path="operator"):

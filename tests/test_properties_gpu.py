@@ -10,6 +10,7 @@ import torch
 
 from instantsplat_amd.diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 from instantsplat_amd.synthetic import syn_blob
+from tests import frame_abi
 from tests.util import settings_for
 
 pytestmark = pytest.mark.gpu
@@ -95,15 +96,14 @@ def _all_tile_lists_sorted_on_device(frame):
     """Every per-tile list of the kept frame: ascending (depth bits, Gaussian index) keys, no duplicates, and together exactly the
     (Gaussian, tile) pairs of the tile rectangles — checked on the device over the whole instance array at once (scratch
     layouts: csrc/common.h).  -> (instances, per-tile counts)"""
-    tiles, geom, binning, W, H, R, P = (frame[k] for k in ("tiles", "geom", "binning", "W", "H", "capacity", "P"))
-    T = ((W + 15) // 16) * ((H + 15) // 16)
-    al = lambda x: (x + 255) & ~255
-    start = tiles[2 * al(T * 4): 2 * al(T * 4) + (T + 1) * 4].view(torch.int32).long()
+    v = frame_abi.FrameViews.of_last_frame(frame)
+    R, P, T, gx = v.R, v.P, v.T, v.gx
+    start = v.tile_start.long()
     n = int(start[T])
     assert 0 < n <= R and int(start[0]) == 0
-    lst = binning[al(R * 8): al(R * 8) + n * 4].view(torch.int32).long()
+    lst = v.list[:n].long()
     assert int(lst.min()) >= 0 and int(lst.max()) < P
-    depth_bits = geom[: P * 48].view(torch.int32).view(P, 12)[:, 11].long()      # the record's depth word (non-negative floats: ordered as ints)
+    depth_bits = v.rec.view(torch.int32)[:, 11].long()                            # the record's depth word (non-negative floats: ordered as ints)
     key = (depth_bits[lst] << 32) | lst
     ascending = key[1:] > key[:-1]
     first_of_tile = torch.zeros(n + 1, dtype=torch.bool, device=key.device)
@@ -112,11 +112,10 @@ def _all_tile_lists_sorted_on_device(frame):
     assert not bool(bad.any()), int(bad.sum())
     # ... and the lists are exactly the (Gaussian, tile) pairs of the projection kernel's tile rectangles: as many instances as
     # the rectangles have tiles, every entry's rectangle contains its tile (with the lists duplicate-free: a bijection)
-    rect = geom[al(P * 48) + al(P * 24): al(P * 48) + al(P * 24) + P * 8].view(torch.int32).view(P, 2).long()
+    rect = v.rect.long()
     x0, y0, x1, y1 = rect[:, 0] & 0xffff, (rect[:, 0] >> 16) & 0xffff, rect[:, 1] & 0xffff, (rect[:, 1] >> 16) & 0xffff
     area = (x1 - x0).clamp(min=0) * (y1 - y0).clamp(min=0)
     assert int(area.sum()) == n, (int(area.sum()), n)
-    gx = (W + 15) // 16
     tile = torch.searchsorted(start[1:].contiguous(), torch.arange(n, device=key.device), right=True)
     tx, ty = tile % gx, tile // gx
     inside = (x0[lst] <= tx) & (tx < x1[lst]) & (y0[lst] <= ty) & (ty < y1[lst])

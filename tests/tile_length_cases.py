@@ -10,7 +10,7 @@ import re
 import numpy as np
 import torch
 
-from tests import ops_util
+from tests import frame_abi, ops_util
 from tests.util import assert_no_worse_than_fp32_oracle, run_custom_case
 
 # The thresholds of csrc/binning.hip and csrc/common.h, restated (test_tile_lengths_emu.py::test_thresholds_are_the_sources holds
@@ -18,8 +18,8 @@ from tests.util import assert_no_worse_than_fp32_oracle, run_custom_case
 SORT_THREADS = 256       # sort_one_tile: one workgroup per tile; 1, 2, 4 or 8 keys per thread, or two runs of (2|4) + (1|2)
 SORT_SMALL_CAP = 2048    # the register network's largest list; longer ones are sorted as runs of this length, placed by rank
 SORT_LDS_CAP = 8192      # ... up to here; longer ones by the bitonic network in global memory
-GS_SEG = 64              # instances per chunk; a backward unit is GS_SEG << level of them
-GS_UNIT_LEVELS = 4
+GS_SEG = frame_abi.GS_SEG             # instances per chunk; a backward unit is GS_SEG << level of them (read from common.h)
+GS_UNIT_LEVELS = frame_abi.GS_UNIT_LEVELS
 MAX_FRAME = 20000        # Gaussians per frame (edge_cases.check_long_tile_lists sends as many through the oracle)
 GRID_X = 6               # tile columns of every frame
 
@@ -195,20 +195,9 @@ def min_units_for(instances, level):
     return mu
 
 
-class at_level:
+def at_level(fr, level):
     """with at_level(frame, level): the knob is set so that the frame runs at that unit level, and restored afterwards"""
-
-    def __init__(self, fr, level):
-        self.mu = min_units_for(fr["n"], level)
-
-    def __enter__(self):
-        from instantsplat_amd import _lib
-        self.L = _lib.lib()
-        self.old = self.L.mi355gs_tune_min_units(0)
-        self.L.mi355gs_tune_min_units(self.mu)
-
-    def __exit__(self, *exc):
-        self.L.mi355gs_tune_min_units(self.old)
+    return frame_abi.knobs(min_units=min_units_for(fr["n"], level))
 
 
 # ---------------------------------------------------------------------------------------------------- exact lists
@@ -217,42 +206,15 @@ def device_lists(dev, fr, fill=0):
     pre-filled with `fill`.  The precondition of every check on these frames is asserted here: each tile's count is the case's,
     and the depth word of every geometry record has the bits of the z handed in.  Returns dict(start, lst, seg_first, part_first,
     meta, count)."""
-    from instantsplat_amd import _lib
-    from instantsplat_amd.camera import Camera
-    dev = torch.device(dev)
-    L = _lib.lib()
     W, H, n = fr["W"], fr["H"], fr["n"]
-    gx, gy = W // 16, H // 16
-    T = gx * gy
-    tanx = math.tan(math.radians(60) / 2)
-    tany = tanx * H / W
-    cam = Camera(0, torch.eye(4), math.radians(60), 2 * math.atan(tany), W, H)
-    t = lambda x: x.float().contiguous().to(dev)
-    means, q, scales, opac, col = map(t, (fr["means"], fr["q"], fr["scales"], fr["opac"].reshape(-1), fr["col"]))
-    view, proj, campos = t(torch.eye(4).reshape(-1)), t(cam.projection_matrix.reshape(-1)), t(torch.zeros(3))
-    geom = torch.zeros(L.mi355gs_raster_geom_bytes(n), dtype=torch.uint8, device=dev)
-    tiles = torch.zeros(L.mi355gs_raster_tiles_bytes(W, H), dtype=torch.uint8, device=dev)
-    radii = torch.zeros(n, dtype=torch.int32, device=dev)
-    nr = torch.zeros(1, dtype=torch.int32, device=dev)
-    p, stream = _lib.ptr, _lib.stream_ptr(dev)
-    _lib.check(L.mi355gs_raster_forward_preprocess(stream, n, 0, 0, W, H, p(means), None, None, p(col), p(opac), p(scales), 1.0, p(q), None,
-                                                   p(view), p(proj), p(campos), tanx, tany, 0, p(radii), p(geom), p(tiles), p(nr), None, None, 0), "preprocess")
-    R = int(nr.item())
+    scene = dict(means=fr["means"], rots=fr["q"], scales=fr["scales"], opac=fr["opac"], colors=fr["col"])
+    res = frame_abi.run_frame(dev, scene, frame_abi.identity_camera(W, H), bg=torch.zeros(3), binning_fill=fill)
+    v, R, radii = res.views, res.R, res.radii
     assert R == n, (R, n)
-    binning = torch.full((L.mi355gs_raster_binning_bytes(R, W, H),), fill, dtype=torch.uint8, device=dev)
-    img, bg = torch.zeros(3, H, W, device=dev), torch.zeros(3, device=dev)
-    _lib.check(L.mi355gs_raster_forward_render(stream, n, W, H, R, p(bg), p(geom), p(tiles), p(binning), p(img), 0), "render")
-    al = lambda x: (x + 255) & ~255
-    # scratch layouts (csrc/common.h).  tiles = count | cursor | start[T+1] | final_T | n_contrib | order | seg_first[T+1] |
-    # part_first[T+1] | meta; binning = keys[R] (8 B) | list[R] (4 B) ...; geom = records (48 B: ... depth last) ...
-    tb = tiles.cpu().numpy()
-    o = 2 * al(T * 4)
-    start = tb[o: o + (T + 1) * 4].view(np.int32).astype(np.int64); o += al((T + 1) * 4) + 2 * al(W * H * 4) + al(T * 4)
-    seg_first = tb[o: o + (T + 1) * 4].view(np.int32).astype(np.int64); o += al((T + 1) * 4)
-    part_first = tb[o: o + (T + 1) * 4].view(np.int32).astype(np.int64); o += al((T + 1) * 4)
-    meta = [int(v) for v in tb[o: o + 16].view(np.int32)]
-    lst = binning[al(R * 8): al(R * 8) + R * 4].cpu().numpy().view(np.uint32).astype(np.int64)
-    depth = geom[: n * 48].cpu().numpy().view(np.uint32).reshape(n, 12)[:, 11].astype(np.int64)
+    T = v.T
+    start, lst, seg_first, part_first = v.np("tile_start"), v.np("list"), v.np("seg_first"), v.np("part_first")
+    meta = [int(x) for x in v.np("meta")]
+    depth = v.np("rec").view(np.uint32)[:, 11].astype(np.int64)     # the depth word of the record
     want = np.array(fr["lengths"] + [0] * (T - len(fr["lengths"])), dtype=np.int64)
     assert start[0] == 0 and start[T] == R
     assert bool((np.diff(start) == want).all()), (np.diff(start).tolist(), want.tolist())

@@ -5,6 +5,7 @@ from instantsplat_amd.synthetic import syn_pointmap
 from instantsplat_amd.train import setup_training
 from instantsplat_amd.gaussian_renderer import render
 from instantsplat_amd import diff_gaussian_rasterization as dgr
+from tests.frame_abi import FrameViews
 dev = torch.device('cuda:0')
 st = setup_training(syn_pointmap(12, 288, 288, 1920, 1080, seed=0), dev)
 g = st.gaussians
@@ -13,9 +14,8 @@ for v in (0, 5):
     cam = st.cameras[v]
     with torch.no_grad():
         render(cam, g, st.pipe, st.background, camera_pose=g.get_RT(cam.uid))
-    tiles, W, H = dgr._LAST_FRAME["tiles"], dgr._LAST_FRAME["W"], dgr._LAST_FRAME["H"]
-    T = ((W + 15) // 16) * ((H + 15) // 16); al = lambda x: (x + 255) & ~255
-    start = tiles[2 * al(T * 4): 2 * al(T * 4) + (T + 1) * 4].cpu().view(torch.int32).numpy().astype(np.int64)
+    views = FrameViews.of_last_frame(dgr._LAST_FRAME)
+    T, start = views.T, views.np("tile_start")
     c = np.diff(start)
     print("view", v, "T", T, "R", int(start[-1]), "mean %.0f median %.0f max %d" % (c.mean(), np.median(c), c.max()))
     edges = [0, 1, 257, 513, 1025, 2049, 4097, 8193, 10**9]
