@@ -721,6 +721,74 @@ int mi355gs_align_init_state(void* workspace, void* stream, int V, int E, int H,
                              float known_focal, const float* srt, const int32_t* pose_row, const float* focals, const int32_t* focal_row,
                              const float* pw_pose, float* pts3d, float* depth_log, float* im_pose, float* focal_log);
 
+/* ----------------------------------------------------------------------------------------------
+ * Adaptive density control (reference scene/gaussian_model.py:328-477 and train.py:195-206): densification statistics, and one
+ * clone / split / prune event as a plan (decisions, counts, scan) and an apply (one ordered scatter of every per-Gaussian row into
+ * the caller's new buffers).  All arrays are device memory, contiguous; every call enqueues on the caller's stream; no allocation,
+ * no memset, no host synchronisation, no atomics (results are the same bits run to run).  Limits (MI355GS_EINVAL beyond them, as
+ * for null required pointers; the scratch-size query then returns 0): P >= 1, 1 <= N <= 8, P (N + 1) <= 2^31 - 1.
+ *
+ *   density_stats (1 launch): for every row with filter[i] != 0 (filter null: radii[i] > 0): grad_accum[i] += sqrt(gx gx + gy gy)
+ *     of grad[i * grad_stride + 0 / 1] (torch's order: square, add, correctly rounded sqrt), denom[i] += 1 and, with radii and
+ *     max_radii given, max_radii[i] = max(max_radii[i], radii[i]).
+ *   density_plan (2 launches): flags say what the event does.
+ *       CLONE   rows with |g| >= max_grad and max(exp(scaling)) <= dense_limit gain a copy (densify_and_clone)
+ *       SPLIT   rows with g >= max_grad and max(exp(scaling)) > dense_limit are replaced by N children (densify_and_split)
+ *       PRUNE   rows are removed: those of `mask` (uint8, non-zero = remove: prune_points), or with mask null those with
+ *               sigmoid(opacity) < min_opacity and, with SCREEN, max_radii > max_screen_size or max(exp(scaling)) > world_limit
+ *               (densify_and_prune:467-471).  The mask is evaluated for the row, for its clone and for its children, whose
+ *               scaling is log(exp(scaling) / child_div), child_div = (float)(0.8 N).
+ *     g is grads[i] (0 for i >= n_grads: the padded gradient) when grads is given, else grad_accum[i] / denom[i] with NaN -> 0.
+ *     Whenever CLONE or SPLIT is set the screen-size term sees radii of 0 for every row, as in the reference, where
+ *     densification_postfix clears max_radii2D before the mask is formed; with PRUNE alone it sees max_radii.  max_radii is read
+ *     in that one form only (PRUNE | SCREEN, no mask, no CLONE / SPLIT), where null is MI355GS_EINVAL; elsewhere it may be null.
+ *     code [P]: bit 0 the row survives, bit 1 it has a surviving clone, bit 2 it is split, bit 3 it was selected for cloning,
+ *     bit 8 + k its child k survives.  scratch: mi355gs_density_scratch_bytes(P, N) bytes, read by density_apply.
+ *     totals_host: null, or 16 int32 of host memory the device can write (pinned, mapped), valid once the stream has passed the
+ *     call: [0] surviving originals, [1] surviving clones, [2] surviving children, [3] rows built and pruned again, [4] rows
+ *     selected for splitting, [5] the new P, [6] rows selected for cloning, [8 + k] first output row of the children of copy k.
+ *   density_apply (1 launch): out rows in the reference's order — surviving originals in index order, surviving clones in index
+ *     order, surviving children of copy 0 in index order, copy 1, ... (`.repeat(N, 1)`: block-repeated).  in / out: host arrays of
+ *     MI355GS_DENSITY_TENSORS device pointers indexed by the constants below; the six parameters are required (f_rest not when
+ *     rest_width, its floats per row, is 0), the others move where both sides are given.  exp_avg / exp_avg_sq: survivors keep
+ *     theirs, appended rows get zeros.  per_point_lr: a clone or child inherits its parent's.  The statistics are zeroed when
+ *     CLONE or SPLIT is set and compacted otherwise.  A child's position is R(q) (exp(scaling) * z) + xyz with R the rotation of
+ *     the normalised raw quaternion and z = noise[k n_selected + rank], rank counting the split rows in index order; noise:
+ *     [noise_rows][3] unit normals, required with noise_rows >= N n_selected when n_selected (totals [4], as the host read it)
+ *     is not 0.  out_rows: rows the out tensors hold (totals [5]); no row beyond it is written.  Every `in` pointer is 16-byte
+ *     aligned, as is out's rotation.
+ *   reset_opacity (1 launch): opacity = inverse_sigmoid(min(sigmoid(opacity), 0.01)) in place; exp_avg / exp_avg_sq (null or [P])
+ *     are zeroed.
+ * ---------------------------------------------------------------------------------------------- */
+#define MI355GS_DENSITY_CLONE 1
+#define MI355GS_DENSITY_SPLIT 2
+#define MI355GS_DENSITY_PRUNE 4
+#define MI355GS_DENSITY_SCREEN 8
+#define MI355GS_DENSITY_XYZ 0
+#define MI355GS_DENSITY_F_DC 1
+#define MI355GS_DENSITY_F_REST 2
+#define MI355GS_DENSITY_OPACITY 3
+#define MI355GS_DENSITY_SCALING 4
+#define MI355GS_DENSITY_ROTATION 5
+#define MI355GS_DENSITY_EXP_AVG 6      /* + the parameter's index */
+#define MI355GS_DENSITY_EXP_AVG_SQ 12  /* + the parameter's index */
+#define MI355GS_DENSITY_PER_POINT_LR 18
+#define MI355GS_DENSITY_GRAD_ACCUM 19
+#define MI355GS_DENSITY_DENOM 20
+#define MI355GS_DENSITY_MAX_RADII 21
+#define MI355GS_DENSITY_TENSORS 22
+int mi355gs_density_stats(void* stream, int P, const float* grad, int grad_stride, const uint8_t* filter, const int32_t* radii,
+                          float* grad_accum, float* denom, float* max_radii);
+size_t mi355gs_density_scratch_bytes(int P, int N);
+int mi355gs_density_plan(void* stream, int P, int N, int flags, const float* grad_accum, const float* denom, const float* grads,
+                         int64_t n_grads, const uint8_t* mask, const float* max_radii, const float* scaling, const float* opacity,
+                         float max_grad, float dense_limit, float min_opacity, float max_screen_size, float world_limit,
+                         float child_div, uint32_t* code, void* scratch, int32_t* totals_host);
+int mi355gs_density_apply(void* stream, int P, int N, int flags, int rest_width, const uint32_t* code, const void* scratch,
+                          const float* noise, int64_t noise_rows, int64_t n_selected, float child_div, const void* const* in,
+                          void* const* out, int64_t out_rows);
+int mi355gs_reset_opacity(void* stream, int P, float* opacity, float* exp_avg, float* exp_avg_sq);
+
 #ifdef __cplusplus
 }
 #endif

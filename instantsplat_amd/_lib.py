@@ -114,6 +114,12 @@ _SIGNATURES = {
     "mi355gs_align_init_apply": (c_int, [_P, c_int, _P, c_int, _P, _P]),
     "mi355gs_align_init_focals": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int64, c_int, _P]),
     "mi355gs_align_init_state": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float] + [_P] * 9),
+    "mi355gs_density_stats": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
+    "mi355gs_density_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "mi355gs_density_plan": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float,
+                                     c_float, c_float, _P, _P, _P]),
+    "mi355gs_density_apply": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int64, c_int64, c_float, _P, _P, c_int64]),
+    "mi355gs_reset_opacity": (c_int, [_P, c_int, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,6 +1,6 @@
 """Gaussian state for the train/render hot path: tensor names, layouts, activations, initialisation
-and optimiser groups of the reference's GaussianModel (reference scene/gaussian_model.py:29-243),
-minus everything that is never executed by InstantSplat (densify/prune, :328-477)."""
+and optimiser groups of the reference's GaussianModel (reference scene/gaussian_model.py:29-243), and its adaptive density
+control (densify / prune, :328-477 — disabled in InstantSplat's own scripts) over density.py."""
 from __future__ import annotations
 
 
@@ -41,8 +41,8 @@ class GaussianModel:
         self.spatial_lr_scale = 0
         self.P = None
         self.test_P = None   # (reference: only ever read, by get_RT_test)
-        # densification statistics of the reference's model (scene/gaussian_model.py:55-57).  Densification is disabled in
-        # InstantSplat (train.py:195-206), so they only exist to keep capture() / restore() tuples interchangeable.
+        # densification statistics of the reference's model (scene/gaussian_model.py:55-57): filled by add_densification_stats,
+        # read and resized by the density events below, and part of the capture() / restore() tuple.
         self.max_radii2D = self.xyz_gradient_accum = self.denom = e
 
     # ---- checkpoint tuple (reference :65-99): same 13 entries in the same order, so a chkpnt<iteration>.pth written by
@@ -196,6 +196,42 @@ class GaussianModel:
                 g["lr"] = self.cam_scheduler_args(iteration)
             if g["name"] == "xyz":
                 g["lr"] = self.xyz_scheduler_args(iteration)
+
+    # ---- adaptive density control (reference :328-477): the reference's method names and signatures over density.py — one plan
+    # call, one read-back and one apply call per event (csrc/density.hip), the optimizer surgery included
+    percent_dense = 0.01   # reference :174 copies it from the training arguments in training_setup; train.training() assigns it
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter, radii=None):
+        """reference :476-478; with `radii` also train.py:198's max_radii2D update, in the same launch."""
+        from . import density
+        density.add_stats(self, viewspace_point_tensor, update_filter, radii)
+
+    def densify_and_clone(self, grads, grad_threshold, scene_extent):
+        from . import density
+        if grads.dim() > 1 and grads.shape[-1] != 1:
+            grads = torch.norm(grads, dim=-1)
+        return density.event(self, density.CLONE, max_grad=grad_threshold, dense_limit=self.percent_dense * scene_extent, grads=grads)
+
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, noise=None):
+        from . import density
+        return density.event(self, density.SPLIT, N=N, max_grad=grad_threshold, dense_limit=self.percent_dense * scene_extent,
+                             grads=grads.squeeze(), noise=noise)
+
+    def prune_points(self, mask):
+        from . import density
+        return density.event(self, density.PRUNE, mask=mask)
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, clone_and_split=False, N=2, noise=None):
+        """reference :460-474.  As written there it only prunes (:464-465 are comments): clone_and_split=False.  With True it
+        is the published 3DGS sequence — clone, then split, then prune — as one event."""
+        from . import density
+        flags = density.PRUNE | ((density.CLONE | density.SPLIT) if clone_and_split else 0)
+        return density.event(self, flags, N=N, max_grad=max_grad, dense_limit=self.percent_dense * extent, min_opacity=min_opacity,
+                             max_screen_size=max_screen_size, world_limit=0.1 * extent, noise=noise)
+
+    def reset_opacity(self):
+        from . import density
+        density.reset_opacity(self)
 
 
 def confidence_to_lr_modifiers(confidence: torch.Tensor, scale=(1.0, 100.0)) -> torch.Tensor:

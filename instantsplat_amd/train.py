@@ -138,8 +138,9 @@ def _pick_camera(st: TrainState):
     return st.viewpoint_stack.pop(st.rng.randint(0, len(st.viewpoint_stack) - 1))
 
 
-def _forward_backward_step(st: TrainState, fused_loss: bool):
-    """Body of reference train.py:140-211 without the host read-back of the loss."""
+def _forward_backward_step(st: TrainState, fused_loss: bool, pkg_out: dict | None = None):
+    """Body of reference train.py:140-211 without the host read-back of the loss.  pkg_out: receives render()'s package (the
+    densification statistics read its screen-space gradient, visibility and radii)."""
     st.iteration += 1
     it, g, opt = st.iteration, st.gaussians, st.opt
     g.update_learning_rate(it)
@@ -152,6 +153,8 @@ def _forward_backward_step(st: TrainState, fused_loss: bool):
     bg = torch.rand(3, device=st.background.device) if opt.random_background else st.background
     with binning_hint(hint_key(st, cam), tag=it):
         pkg = render(cam, g, st.pipe, bg, camera_pose=pose)
+    if pkg_out is not None:
+        pkg_out.update(pkg)
     image = pkg["render"]
     gt = st.gt_images[cam.uid]
     if fused_loss is True:
@@ -172,6 +175,32 @@ def _optimizer_step(st: TrainState):
         if st.iteration < st.opt.iterations:
             st.gaussians.optimizer.step()
             st.gaussians.optimizer.zero_grad(set_to_none=True)
+
+
+def _densify_iteration(st: TrainState, fused_loss, extent: float, white_background: bool, clone_and_split: bool, log: dict):
+    """One pass of reference train.py:140-211 with the comment marks of :195-206 removed, on the drop-in step (where
+    `viewspace_points.grad` exists): statistics every iteration below densify_until_iter, `densify_and_prune` every
+    densification_interval iterations, `reset_opacity` every opacity_reset_interval — before the optimizer step, as there.  The
+    parameters an event replaces have no gradient yet, so that step moves the poses only, as in the reference."""
+    cancel_prepared(st)
+    pkg = {}
+    loss = _forward_backward_step(st, fused_loss, pkg_out=pkg)
+    out = loss.item()
+    it, g, opt = st.iteration, st.gaussians, st.opt
+    with torch.no_grad():
+        if it < opt.densify_until_iter:
+            g.add_densification_stats(pkg["viewspace_points"], pkg["visibility_filter"], radii=pkg["radii"])   # train.py:198-199
+            if it > opt.densify_from_iter and it % opt.densification_interval == 0:
+                size_threshold = 20 if it > opt.opacity_reset_interval else None
+                totals = g.densify_and_prune(opt.densify_grad_threshold, 0.005, extent, size_threshold, clone_and_split=clone_and_split)
+                log["density_events"].append((it, totals))
+                release_trainer(st)   # a one-call handle sized for the old P must not outlive it
+            if it % opt.opacity_reset_interval == 0 or (white_background and it == opt.densify_from_iter):
+                g.reset_opacity()
+                log["opacity_resets"] += 1
+    _optimizer_step(st)
+    st.last_loss = out
+    return out
 
 
 def _host_state(st: TrainState, tr):
@@ -692,7 +721,8 @@ def _save_outputs(st: TrainState, iteration: int, model_path: str, colmap_ids):
 def training(scene, device, iterations: int = 1000, log_every: int = 0, run_ahead: bool = True,
              fused_loss: bool = True, model_path: str | None = None, saving_iterations=(), checkpoint_iterations=(),
              start_checkpoint: str | None = None, opt: OptimizationParams | None = None, n_views: int | None = None,
-             model: ModelParams | None = None, after_setup=None, resolution=1, testing_iterations=()) -> dict:
+             model: ModelParams | None = None, after_setup=None, resolution=1, testing_iterations=(), densify: bool = False,
+             densify_clone_and_split: bool = False) -> dict:
     """Train one scene.  run_ahead=True (default): the fastest loop with the reference's results — the one-call step with every
     iteration's loss read back while the device already works on the next iteration (`train_iteration(fused_step=True)`,
     _fused_synced_iteration) for the configuration the reference's scripts run, the window-verified RunAhead driver on the
@@ -703,6 +733,12 @@ def training(scene, device, iterations: int = 1000, log_every: int = 0, run_ahea
     `n_views` and `-r <resolution>`; loaded with `scene_io.load_init_scene`, which also leaves input.ply and cameras.json in
     `model_path` like the reference's Scene).  opt: the optimisation parameters (default: the scripts' `--pp_optimizer --optim_pose`); its
     `iterations` is overridden by the argument.  after_setup(state): hook between set-up and the first iteration (tests).
+
+    densify: adaptive density control, reference train.py:195-206 with the comment marks removed, driven by `opt`'s
+    percent_dense / densification_interval / opacity_reset_interval / densify_from_iter / densify_until_iter /
+    densify_grad_threshold; it runs on the drop-in step whatever `run_ahead` says.  As written in the reference `densify_and_prune`
+    only prunes; densify_clone_and_split=True restores its clone and split calls (scene/gaussian_model.py:464-465).  The result
+    then also holds "density_events" [(iteration, totals)] and "opacity_resets".  densify=False: nothing changes.
 
     testing_iterations: reference --test_iterations; `training_report` runs at the LAST iteration if it is one of them (train.py:218)
     and its numbers come back under "report".
@@ -744,6 +780,11 @@ def training(scene, device, iterations: int = 1000, log_every: int = 0, run_ahea
         # (the reference's restore() falls back to plain Adam here; a run started with --pp_optimizer keeps its multiplier)
         st.gaussians.restore(model_params, opt, confidence_lr=getattr(st.gaussians, "per_point_lr", None))
         st.iteration = int(first_iter)
+        for g_ in st.gaussians.optimizer.param_groups:
+            # a checkpoint written after a density event holds another number of Gaussians than the scene: the per-point rates that
+            # count are the ones the optimizer's state brought back, not the ones set-up made for the scene's points
+            if g_["name"] == "xyz" and g_.get("per_point_lr") is not None:
+                st.gaussians.per_point_lr = g_["per_point_lr"]
     colmap_ids = [int(c.colmap_id) for c in st.cameras]
     saving, checkpoints = set(int(i) for i in saving_iterations), set(int(i) for i in checkpoint_iterations)
     if (saving or checkpoints) and not model_path:
@@ -767,12 +808,22 @@ def training(scene, device, iterations: int = 1000, log_every: int = 0, run_ahea
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         first = last = None
-        one_call = bool(run_ahead and fused_loss and FusedTrainer.supported(st))
-        ra = RunAhead(st, fused_loss=fused_loss) if run_ahead and not one_call else None
+        one_call = bool(run_ahead and fused_loss and not densify and FusedTrainer.supported(st))
+        ra = RunAhead(st, fused_loss=fused_loss) if run_ahead and not one_call and not densify else None
         ema = 0.0
         report = {}
+        density_log = {"density_events": [], "opacity_resets": 0}
+        if densify:
+            st.gaussians.percent_dense = opt.percent_dense   # reference scene/gaussian_model.py:174
+            extent = float(scene.extent if isinstance(scene, PointmapScene) else scene.cameras_extent)
+            white_background = bool((model or ModelParams()).white_background)
         for i in range(int(first_iter), iterations):
-            if one_call:
+            if densify:
+                last = _densify_iteration(st, fused_loss, extent, white_background, densify_clone_and_split, density_log)
+                first = last if first is None else first
+                if log_every and (i + 1) % log_every == 0:
+                    print(f"[iter {i + 1}] loss {last:.6f}  P {st.gaussians._xyz.shape[0]}")
+            elif one_call:
                 last = train_iteration(st, fused_step=True)
                 first = last if first is None else first
                 ema = 0.4 * last + 0.6 * ema   # reference train.py:188
@@ -822,5 +873,8 @@ def training(scene, device, iterations: int = 1000, log_every: int = 0, run_ahea
     if model_path:   # reference train.py:229-231
         save_time(model_path, "[2] train_joint", dt)
     n_done = max(iterations - int(first_iter), 1)
-    return dict(seconds=dt, iters_per_sec=n_done / dt, first_loss=first, last_loss=last, psnr_before=psnr0,
-                psnr_after=evaluate_psnr(st), state=st, report=report)
+    out = dict(seconds=dt, iters_per_sec=n_done / dt, first_loss=first, last_loss=last, psnr_before=psnr0,
+               psnr_after=evaluate_psnr(st), state=st, report=report)
+    if densify:
+        out.update(density_log)
+    return out
