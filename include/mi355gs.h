@@ -789,6 +789,36 @@ int mi355gs_density_apply(void* stream, int P, int N, int flags, int rest_width,
                           void* const* out, int64_t out_rows);
 int mi355gs_reset_opacity(void* stream, int P, float* opacity, float* exp_avg, float* exp_avg_sq);
 
+/* ----------------------------------------------------------------------------------------------
+ * Resizing 8-bit RGB images on the device (csrc/resample.hip): PIL's `Image.resize` for 8-bit images, byte for byte, with the
+ * crop and the conversion to float that follow it in the reference's loaders (utils/general_utils.py:21-27 PILtoTorch;
+ * dust3r/utils/image.py:63-70,73-126 load_images).  images: uint8 [N][H][W][3] in device memory, any base address; the call
+ * resizes each to Hout x Wout and produces the window x0 <= x < x0 + w, y0 <= y < y0 + h of the result.
+ *   Tables (device memory, built by the caller as PIL's precompute_coeffs + normalize_coeffs_8bpc build them:
+ *   instantsplat_amd/resample.py `resample_coeffs`): kx int32 [Wout][ksize_x], coefficients with 22 fractional bits, and bx int32
+ *   [Wout][2] = (first source column, number of taps) per output column; ky [Hout][ksize_y] and by [Hout][2] likewise for rows.
+ *   kx NULL: the horizontal pass is skipped, Wout must equal W; ky NULL: the vertical pass is skipped, Hout must equal H.
+ *   Arithmetic, per pass and channel: acc = 2^21 + sum over the taps of k[t] * byte[first + t] in 32-bit integers, result =
+ *   clip(acc >> 22, 0, 255); a coefficient enters as its low 24 bits, signed (PIL's stay below 2^23 in magnitude), and the sum wraps.
+ *   The horizontal pass runs first and stores 8 bits, as PIL's does.  Taps that a table places outside
+ *   the image (or outside its row of the table) are not read, whatever the tables hold.
+ *   Outputs, each NULL or device memory, one of them at least, all written by the last pass that runs:
+ *     rgb8 uint8 [N][h][w][3]; unit float [N][3][h][w] = (float)v / 255.0f; normalized float [N][3][h][w] =
+ *     ((float)v / 255.0f - 0.5f) / 0.5f, every operation in IEEE float32, rounded once.
+ *   row0, rows, scratch: read only when both passes run.  The horizontal pass then produces the source rows row0 .. row0+rows-1
+ *   for the window's columns into scratch (mi355gs_resample_rgb8_scratch_bytes(N, rows, w) bytes of device memory, owned by the
+ *   caller): the rows the window's vertical taps reach, i.e. by[y0][0] .. by[y0+h-1][0] + by[y0+h-1][1] - 1.
+ * Launches: one per pass that runs; one copy / convert launch when both are skipped.  On the caller's stream; no host
+ * synchronisation, no allocation, no memset, no atomics.  Limits (MI355GS_EINVAL beyond them, as for null images, no output, a
+ * window outside the result, a missing bounds table or ksize <= 0 beside a table, a size change without its table, a null
+ * scratch or a row range outside the source when both passes run; the scratch query then returns 0): N and every size
+ * <= 65535, 3 H W and 3 Hout Wout <= 2^31 - 1.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi355gs_resample_rgb8_scratch_bytes(int N, int rows, int w);
+int mi355gs_resample_rgb8(void* stream, int N, int H, int W, int Hout, int Wout, const uint8_t* images, const int32_t* kx,
+                          const int32_t* bx, int ksize_x, const int32_t* ky, const int32_t* by, int ksize_y, int x0, int y0, int w,
+                          int h, int row0, int rows, void* scratch, uint8_t* rgb8, float* unit, float* normalized);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,9 @@ _SIGNATURES = {
                                      c_float, c_float, _P, _P, _P]),
     "mi355gs_density_apply": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int64, c_int64, c_float, _P, _P, c_int64]),
     "mi355gs_reset_opacity": (c_int, [_P, c_int, _P, _P, _P]),
+    "mi355gs_resample_rgb8_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355gs_resample_rgb8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -13,6 +13,7 @@ What the reference does between `init_geo.py`'s output directory and the first t
                            the scale of the position learning rate (scene/__init__.py:71,94)
   load_cam                 utils/camera_utils.py:21-54 + utils/general_utils.py:21-27 (PILtoTorch): the image at `-r <resolution>`
                            as float32 [3,H,W] in [0,1]; width / height of the camera come from the IMAGE, FoV from cameras.txt
+                           (resize="device": the same image, resized by resample.resize_rgb8 instead of PIL)
   scale_from_view_depth    utils/graphics_utils.py:107-135 (`--init_scale_from_view_depth`, off in the reference's scripts)
   load_cameras             scene/dataset_readers.py:75-104 (loadCameras): stored poses (pose_optimized.npy, an interpolated path) back
                            into the cameras, as render.py:206-207,235-236 does before it renders with them
@@ -22,7 +23,8 @@ What the reference does between `init_geo.py`'s output directory and the first t
   write_init_scene         the inverse, for tests and for exporting a synthetic scene: the same files utils/sfm_utils.py:202-316
                            writes (text models, points3D.ply, confidence_dsp.npy) + images/*.png
 
-Host-side only: nothing here launches a kernel; `train.setup_training()` takes the result to the device path.
+Host-side only, but for load_cam(resize="device"): nothing else here launches a kernel; `train.setup_training()` takes the result
+to the device path.
 """
 from __future__ import annotations
 
@@ -168,8 +170,23 @@ def image_resolution(orig_w: int, orig_h: int, resolution, resolution_scale: flo
     return int(orig_w / scale), int(orig_h / scale)
 
 
-def load_cam(info: CameraInfo, uid: int, resolution=1, resolution_scale: float = 1.0, device="cuda") -> Camera:
-    img = pil_to_torch(info.image, image_resolution(*info.image.size, resolution, resolution_scale))
+def device_pil_to_torch(pil_image, resolution, device) -> torch.Tensor:
+    """`pil_to_torch` with the resize on the device (resample.resize_rgb8: PIL's default BICUBIC, the same bytes, `/ 255.0`): the
+    image's bytes are uploaded as they are and the float32 [3,H,W] result stays on `device`.  8-bit RGB images only."""
+    from .resample import resize_rgb8
+    if pil_image.mode != "RGB":
+        raise ValueError(f'load_cam(resize="device") takes 8-bit RGB images, got mode {pil_image.mode!r}: use resize="pil"')
+    source = torch.from_numpy(np.array(pil_image)).to(device)
+    return resize_rgb8(source, resolution, resample="bicubic", out="unit")
+
+
+def load_cam(info: CameraInfo, uid: int, resolution=1, resolution_scale: float = 1.0, device="cuda", resize: str = "pil") -> Camera:
+    """resize: "pil" (default) resizes with PIL on the host, as the reference does; "device" uploads the image's bytes and resizes
+    them there — the same image bit for bit.  An image already at the target size is resampled by neither (PIL copies it)."""
+    if resize not in ("pil", "device"):
+        raise ValueError(f'resize must be "pil" or "device", got {resize!r}')
+    target = image_resolution(*info.image.size, resolution, resolution_scale)
+    img = pil_to_torch(info.image, target) if resize == "pil" else device_pil_to_torch(info.image, target, device)
     # (the reference looks for an alpha channel with `shape[1] == 4` — the image HEIGHT — so RGBA inputs lose their alpha without
     # being masked by it; only the first three channels are ever used)
     gt = img[:3, ...].to(torch.float32)
