@@ -208,6 +208,34 @@ def ptr(t: torch.Tensor | None):
     return None if t is None else t.data_ptr()
 
 
+STREAM = object()   # in the arguments of `call`: where the entry point takes the stream (first, or second after a handle)
+
+
+def call(dev, name: str, *args):
+    """mi355gs_<name>(*args) for the tensors on `dev`: under `on_device(dev)`, a tensor passed as its address, None as NULL,
+    STREAM as the current stream of `dev`, everything else as it is; a non-zero return code raises as `check` words it.
+    For the stage wrappers.  The per-iteration hot paths (diff_gaussian_rasterization, fused, fused_ssim, lazy_loss, loss_utils,
+    optim, FusedTrainer.prepare/launch/step/apply_optimizer, RunAhead) stay off it on purpose: they go through the compiled binding
+    or were tuned call by call."""
+    fn = getattr(lib(), "mi355gs_" + name)
+    with on_device(dev):
+        check(fn(*[stream_ptr(dev) if a is STREAM else a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]), name)
+
+
+def scratch(dev, name: str, *sizes, what: str | None):
+    """The uint8 scratch block of mi355gs_<name>(*sizes) bytes on `dev`.  A query that answers 0 refuses the sizes: ValueError(what).
+    what=None: for a query that refuses nothing, and whose block may be empty (one byte then: an empty tensor has no address)."""
+    nbytes = int(getattr(lib(), "mi355gs_" + name)(*sizes))
+    if not nbytes and what is not None:
+        raise ValueError(what)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+
+
+def gpu_only(who: str = "instantsplat_amd operators run") -> str:
+    """the one wording of the refusal of CPU tensors"""
+    return f"{who} on the GPU only (got a CPU tensor; there is no CPU fallback)"
+
+
 _F32 = torch.float32
 
 
@@ -222,7 +250,7 @@ def f32c_on_one_device(*tensors):
         d = t.device
         if dev is None:
             if d.type != "cuda" and not _TEST_MODE:
-                raise RuntimeError("instantsplat_amd operators run on the GPU only (got a CPU tensor; there is no CPU fallback)")
+                raise RuntimeError(gpu_only())
             dev = d
         elif d != dev:
             raise RuntimeError(f"tensors on different devices: {dev} vs {d}")
@@ -237,7 +265,7 @@ def require_device(*tensors: torch.Tensor | None):
         if t is None:
             continue
         if not t.is_cuda and not _TEST_MODE:
-            raise RuntimeError("instantsplat_amd operators run on the GPU only (got a CPU tensor; there is no CPU fallback)")
+            raise RuntimeError(gpu_only())
         if not t.is_contiguous():
             raise RuntimeError("instantsplat_amd operators need contiguous tensors")
         if dev is None:

@@ -97,9 +97,7 @@ def add_stats(model, viewspace_point_tensor, update_filter, radii=None):
     dev = _lib.require_device(grad, filt, accum, denom, radii, maxr)
     if P == 0:
         return
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().mi355gs_density_stats(_lib.stream_ptr(dev), P, _lib.ptr(grad), int(grad.shape[1]), _lib.ptr(filt),
-                                                    _lib.ptr(radii), _lib.ptr(accum), _lib.ptr(denom), _lib.ptr(maxr)), "density_stats")
+    _lib.call(dev, "density_stats", _lib.STREAM, P, grad, int(grad.shape[1]), filt, radii, accum, denom, maxr)
     # (reshape / contiguous hand back the same storage for the layouts training_setup creates; anything else is written back)
     for name, t in (("xyz_gradient_accum", accum), ("denom", denom), ("max_radii2D", maxr)):
         if t is not None and t.data_ptr() != getattr(model, name).data_ptr():
@@ -158,41 +156,33 @@ def event(model, flags, N=2, max_grad=0.0, dense_limit=0.0, min_opacity=0.0, max
         raise RuntimeError("pruning by screen size needs the model's max_radii2D")
     dev = _lib.require_device(*ins, grads, mask, noise)
     is_cuda = dev.type == "cuda"
-    L = _lib.lib()
-    nbytes = int(L.mi355gs_density_scratch_bytes(P, N))
-    if nbytes == 0:
-        raise ValueError(f"density control: P = {P} with N = {N} is beyond the kernels' limits")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(dev, "density_scratch_bytes", P, N, what=f"density control: P = {P} with N = {N} is beyond the kernels' limits")
     code = torch.empty(P, dtype=torch.int32, device=dev)
     word = torch.full((16,), -1, dtype=torch.int32, pin_memory=is_cuda)
     child_div = 0.8 * N
-    with _lib.on_device(dev):
-        _lib.check(L.mi355gs_density_plan(
-            _lib.stream_ptr(dev), P, N, flags, _lib.ptr(ins[GRAD_ACCUM]), _lib.ptr(ins[DENOM]), _lib.ptr(grads), n_grads, _lib.ptr(mask),
-            _lib.ptr(ins[MAX_RADII]), _lib.ptr(ins[4]), _lib.ptr(ins[3]), float(max_grad), float(dense_limit), float(min_opacity),
-            float(max_screen_size or 0.0), float(world_limit), child_div, _lib.ptr(code), _lib.ptr(scratch), _lib.ptr(word)), "density_plan")
-        if is_cuda:
-            torch.cuda.current_stream(dev).synchronize()   # the one read-back of the event: 16 words the scan kernel stored
-        totals = [int(v) for v in word.tolist()]
-        new_P, n_sel = totals[5], totals[4]
-        if not (0 <= new_P <= P * (N + 1) and 0 <= n_sel <= P):
-            raise RuntimeError(f"density_plan: the totals hold new P = {new_P}, split = {n_sel} for P = {P}")
-        if n_sel > 0:
-            if noise is None:
-                noise = torch.randn(N * n_sel, 3, dtype=torch.float32, device=dev)
-            else:
-                noise = _lib.f32c(noise)
-                if noise.dim() != 2 or noise.shape[1] != 3 or noise.shape[0] < N * n_sel:
-                    raise ValueError(f"noise must be [>= {N * n_sel}, 3] for {n_sel} split Gaussians, got {list(noise.shape)}")
+    _lib.call(dev, "density_plan", _lib.STREAM, P, N, flags, ins[GRAD_ACCUM], ins[DENOM], grads, n_grads, mask, ins[MAX_RADII], ins[4], ins[3],
+              float(max_grad), float(dense_limit), float(min_opacity), float(max_screen_size or 0.0), float(world_limit), child_div, code,
+              scratch, word)
+    if is_cuda:
+        torch.cuda.current_stream(dev).synchronize()   # the one read-back of the event: 16 words the scan kernel stored
+    totals = [int(v) for v in word.tolist()]
+    new_P, n_sel = totals[5], totals[4]
+    if not (0 <= new_P <= P * (N + 1) and 0 <= n_sel <= P):
+        raise RuntimeError(f"density_plan: the totals hold new P = {new_P}, split = {n_sel} for P = {P}")
+    if n_sel > 0:
+        if noise is None:
+            noise = torch.randn(N * n_sel, 3, dtype=torch.float32, device=dev)
         else:
-            noise = None
-        outs = [None if t is None else torch.empty((new_P,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in ins]
-        if new_P > 0:
-            PTR = ctypes.c_void_p * N_TENSORS
-            _lib.check(L.mi355gs_density_apply(
-                _lib.stream_ptr(dev), P, N, flags, rest_width, _lib.ptr(code), _lib.ptr(scratch), _lib.ptr(noise),
-                0 if noise is None else int(noise.shape[0]), n_sel, child_div, PTR(*[_lib.ptr(t) for t in ins]),
-                PTR(*[_lib.ptr(t) for t in outs]), new_P), "density_apply")
+            noise = _lib.f32c(noise)
+            if noise.dim() != 2 or noise.shape[1] != 3 or noise.shape[0] < N * n_sel:
+                raise ValueError(f"noise must be [>= {N * n_sel}, 3] for {n_sel} split Gaussians, got {list(noise.shape)}")
+    else:
+        noise = None
+    outs = [None if t is None else torch.empty((new_P,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev) for t in ins]
+    if new_P > 0:
+        PTR = ctypes.c_void_p * N_TENSORS
+        _lib.call(dev, "density_apply", _lib.STREAM, P, N, flags, rest_width, code, scratch, noise, 0 if noise is None else int(noise.shape[0]),
+                  n_sel, child_div, PTR(*[_lib.ptr(t) for t in ins]), PTR(*[_lib.ptr(t) for t in outs]), new_P)
     # ---- the optimizer surgery (reference :328-398): each group's parameter is replaced and its state moves under the new one
     opt = model.optimizer
     with torch.no_grad():
@@ -235,8 +225,7 @@ def reset_opacity(model):
         m, v = torch.empty_like(new), torch.empty_like(new)
     dev = _lib.require_device(new, m, v)
     if P > 0:
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().mi355gs_reset_opacity(_lib.stream_ptr(dev), P, _lib.ptr(new), _lib.ptr(m), _lib.ptr(v)), "reset_opacity")
+        _lib.call(dev, "reset_opacity", _lib.STREAM, P, new, m, v)
     new_p = nn.Parameter(new.requires_grad_(True))
     if "opacity" in groups:
         group = groups["opacity"][0]

@@ -108,6 +108,17 @@ class BinningPolicy:
     mode = "exact"
     slack = 1.5
     pad = 16384
+
+    @classmethod
+    def capacity_for(cls, count) -> int:
+        """the instance capacity for a frame whose count was last seen as `count` (the product is truncated)"""
+        return int(cls.slack * count) + cls.pad
+
+    @classmethod
+    def regrown(cls, count, capacity) -> int:
+        """the capacity after a frame of `count` instances outgrew `capacity`: at least twice the old one"""
+        return max(cls.capacity_for(count), 2 * capacity)
+
     known = {}       # key -> last verified R
     pending = []     # _Pending
     current_key = None

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .handles import LibraryHandle
 
 MAX_VIEWS = 256
 MAX_EDGES = 65535
@@ -50,12 +51,14 @@ def _f32(x, shape, what, dev):
     return t.detach().contiguous()
 
 
-class AlignProblem:
+class AlignProblem(LibraryHandle):
     """The fixed side of one alignment: V images of H x W, E directed edges (i, j) covering every image (any list: it need not
     be symmetrised, an image may appear only as a j), the pairwise pointmaps pred_i / pred_j [E,H*W,3] (or [E,H,W,3]) and raw
     confidences conf_i / conf_j [E,H*W] >= 1 (the reference's _stacked_pred_i / _j, conf_i / conf_j), and the switches: which
     parameter groups take Adam steps (the reference's requires_grad: optimize_im_poses is off after `preset_pose`, which also
     turns norm_pw_scale off; optimize_focals is off under --focal_avg / known_focal) and norm_pw_scale."""
+    prefix = "align"
+    _handle = property(lambda self: self.handle)   # (the name the tests and tools know it by)
 
     def __init__(self, edges, pred_i, pred_j, conf_i, conf_j, H, W, *, optimize_depth=True, optimize_im_poses=True, optimize_focals=True,
                  optimize_pw_poses=True, norm_pw_scale=True, base_scale=0.5):
@@ -82,32 +85,17 @@ class AlignProblem:
         self.conf_j = _f32(conf_j.reshape(E, n), (E, n), "conf_j", dev)
         pred_i = _f32(pred_i.reshape(E, n, 3), (E, n, 3), "pred_i", dev)
         pred_j = _f32(pred_j.reshape(E, n, 3), (E, n, 3), "pred_j", dev)
-        L = _lib.lib()
-        nbytes = int(L.mi355gs_align_workspace_bytes(V, H, W, E, self.flags))
         host_edges = (ctypes.c_int32 * (2 * E))(*[x for e in edges for x in e])
-        self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        self._handle = L.mi355gs_align_create(_lib.ptr(self._workspace), V, H, W, host_edges, E, self.flags, self.base_scale) if nbytes else None
-        if not self._handle:
-            self._handle = None
-            raise ValueError(f"mi355gs_align_create refused {V} images of {H} x {W} with {E} edges (include/mi355gs.h: V <= {MAX_VIEWS}, "
+        refused = ValueError(f"mi355gs_align_create refused {V} images of {H} x {W} with {E} edges (include/mi355gs.h: V <= {MAX_VIEWS}, "
                              f"E <= {MAX_EDGES}, E H W <= 2^31 - 1, every image covered by an edge, no edge from an image to itself)")
-        with _lib.on_device(dev):
-            _lib.check(L.mi355gs_align_pack(self._handle, _lib.stream_ptr(dev), _lib.ptr(pred_i), _lib.ptr(pred_j), _lib.ptr(self.conf_i),
-                                            _lib.ptr(self.conf_j)), "align_pack")
-            if dev.type == "cuda":
-                torch.cuda.current_stream(dev).synchronize()   # pred_i / pred_j may go once the records are written
+        self._open(dev, (V, H, W, E, self.flags), lambda ws: (ws, V, H, W, host_edges, E, self.flags, self.base_scale), refused, refused)
+        _lib.call(dev, "align_pack", self._h, _lib.STREAM, pred_i, pred_j, self.conf_i, self.conf_j)
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()   # pred_i / pred_j may go once the records are written
 
     @classmethod
     def from_arrays(cls, *args, **kwargs):
         return cls(*args, **kwargs)
-
-    def __del__(self):
-        h, self._handle = getattr(self, "_handle", None), None
-        if h:
-            try:
-                _lib.lib().mi355gs_align_destroy(h)
-            except Exception:
-                pass
 
     def im_conf(self) -> torch.Tensor:
         """`_compute_img_conf` (base_opt.py:137-143): per image the element-wise maximum of the raw confidences over every edge
@@ -179,9 +167,7 @@ class AlignState:
         P = self.problem
         pts = torch.empty(P.V, P.H, P.W, 3, dtype=torch.float32, device=P.device)
         depth = torch.empty(P.V, P.H, P.W, dtype=torch.float32, device=P.device)
-        with _lib.on_device(P.device):
-            _lib.check(_lib.lib().mi355gs_align_points(P._handle, _lib.stream_ptr(P.device), *self._state_ptrs(), _lib.ptr(pts), _lib.ptr(depth)),
-                       "align_points")
+        _lib.call(P.device, "align_points", P._h, _lib.STREAM, *self._state_ptrs(), pts, depth)
         return pts, depth
 
     def pts3d(self) -> torch.Tensor:
@@ -274,21 +260,16 @@ def global_alignment(problem: AlignProblem, state: AlignState, niter=300, lr=0.0
     if niter == 0 or not (problem.flags & (OPT_DEPTH | OPT_IM_POSES | OPT_FOCALS | OPT_PW_POSES)):
         return float("inf"), losses[:0]   # (with nothing to optimise the reference returns before its loop, base_opt.py:327-329)
     table = torch.from_numpy(step_table(state.step, niter, float(lr), schedule, float(lr_min))).to(dev)
-    moments = [_lib.ptr(t) for k in ("depth_log", "im_pose", "focal_log", "pw_pose") for t in state.moments[k]]
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().mi355gs_align_run(problem._handle, _lib.stream_ptr(dev), niter, _lib.ptr(table), *state._state_ptrs(), *moments,
-                                                _lib.ptr(losses)), "align_run")
+    moments = [t for k in ("depth_log", "im_pose", "focal_log", "pw_pose") for t in state.moments[k]]
+    _lib.call(dev, "align_run", problem._h, _lib.STREAM, niter, table, *state._state_ptrs(), *moments, losses)
     state.step += niter
     return float(losses[-1]), losses   # (the read of the last loss also keeps `table` alive until the run has finished)
 
 
 # ------------------------------------------------------------------------------------------------ the initialisation (csrc/align_init.hip)
 def _init_workspace(dev, B, n):
-    nbytes = int(_lib.lib().mi355gs_align_init_workspace_bytes(int(B), int(n)))
-    if not nbytes:
-        raise ValueError(f"mi355gs_align_init_workspace_bytes refused {B} jobs of {n} points (include/mi355gs.h: 1 <= B <= {MAX_EDGES}, "
-                         f"n >= 1, B n <= 2^31 - 1)")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return _lib.scratch(dev, "align_init_workspace_bytes", int(B), int(n), what=f"mi355gs_align_init_workspace_bytes refused {B} jobs of {n} "
+                        f"points (include/mi355gs.h: 1 <= B <= {MAX_EDGES}, n >= 1, B n <= 2^31 - 1)")
 
 
 def register_points(x, y, weights=None):
@@ -307,9 +288,7 @@ def register_points(x, y, weights=None):
     w = None if weights is None else _f32(weights, (B, n), "weights", dev)
     ws = _init_workspace(dev, B, n)
     srt = torch.empty(B, 16, dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().mi355gs_align_init_register(_lib.ptr(ws), _lib.stream_ptr(dev), B, n, _lib.ptr(x), None, 3 * n, 3, _lib.ptr(y), None,
-                                                          3 * n, _lib.ptr(w), None, n, _lib.ptr(srt), None), "align_init_register")
+    _lib.call(dev, "align_init_register", ws, _lib.STREAM, B, n, x, None, 3 * n, 3, y, None, 3 * n, w, None, n, srt, None)
     return srt[:, 0].clone(), srt[:, 1:10].reshape(B, 3, 3).clone(), srt[:, 10:13].clone()
 
 
@@ -404,7 +383,7 @@ def init_minimum_spanning_tree(problem: AlignProblem, *, focal_avg=False, known_
 
     focal_avg / known_focal freeze the focals in the reference (`preset_focal`); a problem's switches are fixed when it is made,
     so either is refused on a problem built without optimize_focals=False."""
-    P, L = problem, _lib.lib()
+    P = problem
     if not P.flags & OPT_IM_POSES:
         raise ValueError("optimize_im_poses=False: the known-poses branch of init_from_pts3d (init_im_poses.py:95-106) is out of scope")
     if (focal_avg or known_focal is not None) and P.flags & OPT_FOCALS:
@@ -412,95 +391,89 @@ def init_minimum_spanning_tree(problem: AlignProblem, *, focal_avg=False, known_
     if known_focal is not None and not float(known_focal) > 0:
         raise ValueError(f"known_focal = {known_focal}: a positive focal expected")
     dev, V, E, n, H, W = P.device, P.V, P.E, P.H * P.W, P.H, P.W
-    st = _lib.stream_ptr(dev)
     ws = _init_workspace(dev, max(E, V), n)
+    run = lambda name, *args: _lib.call(dev, "align_init_" + name, *args)       # noqa: E731
     i32 = lambda values: torch.tensor(list(values), dtype=torch.int32).to(dev)   # noqa: E731
-    with _lib.on_device(dev):
-        means = torch.empty(2 * E, dtype=torch.float32, device=dev)
-        _lib.check(L.mi355gs_align_init_means(_lib.ptr(ws), st, E, n, _lib.ptr(P.conf_i), _lib.ptr(means)), "align_init_means")
-        _lib.check(L.mi355gs_align_init_means(_lib.ptr(ws), st, E, n, _lib.ptr(P.conf_j), _lib.ptr(means) + 4 * E), "align_init_means")
-        m = means.cpu().numpy()                                                  # the one synchronisation
-        scores = {e: float(m[k] * m[E + k]) for k, e in enumerate(P.edges)}      # commons.py:20-25
-        tree = spanning_tree(scores, V)
-        if len(tree) != V - 1:
-            raise ValueError("the edges do not connect every image: no spanning tree (the reference's walk would not end)")
-        plan = walk_plan(tree, P.edges, scores)
-        if focal_avg and len(plan["focal_edge"]) != V:
-            missing = sorted(set(range(V)) - set(plan["focal_edge"]))
-            raise ValueError(f"focal_avg: images {missing} are never the first image of an edge and have no focal estimate "
-                             "(the reference fails there too)")
+    means = torch.empty(2 * E, dtype=torch.float32, device=dev)
+    run("means", ws, _lib.STREAM, E, n, P.conf_i, means)
+    run("means", ws, _lib.STREAM, E, n, P.conf_j, means[E:])
+    m = means.cpu().numpy()                                                  # the one synchronisation
+    scores = {e: float(m[k] * m[E + k]) for k, e in enumerate(P.edges)}      # commons.py:20-25
+    tree = spanning_tree(scores, V)
+    if len(tree) != V - 1:
+        raise ValueError("the edges do not connect every image: no spanning tree (the reference's walk would not end)")
+    plan = walk_plan(tree, P.edges, scores)
+    if focal_avg and len(plan["focal_edge"]) != V:
+        missing = sorted(set(range(V)) - set(plan["focal_edge"]))
+        raise ValueError(f"focal_avg: images {missing} are never the first image of an edge and have no focal estimate "
+                         "(the reference fails there too)")
 
-        # every index table is uploaded here, while the stream is idle: a host-to-device copy behind enqueued kernels would wait for them
-        n_steps = len(plan["steps"])
-        focal_images = sorted(plan["focal_edge"])
-        focal_row = {v: k for k, v in enumerate(focal_images)}
-        src_idx = i32(2 * plan["focal_edge"][v] for v in focal_images)
-        pair_src, pair_tgt = i32(2 * e for e in range(E)), i32(i for i, j in P.edges)
-        pose_row = [-1] * V
+    # every index table is uploaded here, while the stream is idle: a host-to-device copy behind enqueued kernels would wait for them
+    n_steps = len(plan["steps"])
+    focal_images = sorted(plan["focal_edge"])
+    focal_row = {v: k for k, v in enumerate(focal_images)}
+    src_idx = i32(2 * plan["focal_edge"][v] for v in focal_images)
+    pair_src, pair_tgt = i32(2 * e for e in range(E)), i32(i for i, j in P.edges)
+    pose_row = [-1] * V
+    for v in range(V):
+        if v in plan["pose_step"]:
+            pose_row[v] = plan["pose_step"][v]
+        elif pnp_fn is None and v in plan["best_edge_of"]:
+            # the stand-in for PnP: the pair registration of the best edge of v IS the registration of v's own-frame pointmap
+            # onto pts3d[v] — its row of the pair batch is the pose
+            pose_row[v] = n_steps + plan["best_edge_of"][v]
+    if pnp_fn is None:
+        pose_row_d, focal_row_d = i32(pose_row), i32(focal_row.get(v, -1) for v in range(V))
+    recs = int(_lib.lib().mi355gs_align_records(P._h))
+    rec = lambda e, side: recs + 16 * n * (2 * e + side)                     # noqa: E731
+    pts3d = torch.empty(V, n, 3, dtype=torch.float32, device=dev)
+    img = lambda v: _lib.ptr(pts3d) + 12 * n * v                             # noqa: E731
+    srt = torch.zeros(n_steps + E + V, 16, dtype=torch.float32, device=dev)  # walk rows, pair rows, rows of pnp_fn
+    row = lambda k: _lib.ptr(srt) + 64 * k                                   # noqa: E731
+    e0, i0, j0 = plan["first"]
+    run("apply", _lib.STREAM, n, rec(e0, 0), 4, None, img(i0))
+    run("apply", _lib.STREAM, n, rec(e0, 1), 4, None, img(j0))
+    for k, (e, side, i, j) in enumerate(plan["steps"]):
+        known, new = (i, j) if side == 0 else (j, i)
+        conf = (P.conf_i if side == 0 else P.conf_j)[e]
+        run("register", ws, _lib.STREAM, 1, n, rec(e, side), None, 0, 4, img(known), None, 0, conf, None, 0, row(k), None)
+        run("apply", _lib.STREAM, n, rec(e, 1 - side), 4, row(k), img(new))
+
+    # focals: one batch over the images that have a source record (they do not depend on the walk's results)
+    focals = torch.zeros(len(focal_images) + V, dtype=torch.float32, device=dev)   # the estimates, then pnp_fn's
+    run("focals", ws, _lib.STREAM, len(focal_images), H, W, recs, src_idx, 4 * n, 4, focals)
+
+    # pair poses: every edge's pred_i onto pts3d[i], weights conf_i (init_im_poses.py:109-113)
+    pw_pose = torch.empty(E, 8, dtype=torch.float32, device=dev)
+    run("register", ws, _lib.STREAM, E, n, recs, pair_src, 4 * n, 4, pts3d, pair_tgt, 3 * n, P.conf_i, None, n, row(n_steps), pw_pose)
+
+    if pnp_fn is not None:
+        im_conf, host_focals = P.im_conf(), None
         for v in range(V):
             if v in plan["pose_step"]:
-                pose_row[v] = plan["pose_step"][v]
-            elif pnp_fn is None and v in plan["best_edge_of"]:
-                # the stand-in for PnP: the pair registration of the best edge of v IS the registration of v's own-frame pointmap
-                # onto pts3d[v] — its row of the pair batch is the pose
-                pose_row[v] = n_steps + plan["best_edge_of"][v]
-        if pnp_fn is None:
-            pose_row_d, focal_row_d = i32(pose_row), i32(focal_row.get(v, -1) for v in range(V))
-        recs = int(L.mi355gs_align_records(P._handle))
-        rec = lambda e, side: recs + 16 * n * (2 * e + side)                     # noqa: E731
-        pts3d = torch.empty(V, n, 3, dtype=torch.float32, device=dev)
-        img = lambda v: _lib.ptr(pts3d) + 12 * n * v                             # noqa: E731
-        srt = torch.zeros(n_steps + E + V, 16, dtype=torch.float32, device=dev)  # walk rows, pair rows, rows of pnp_fn
-        row = lambda k: _lib.ptr(srt) + 64 * k                                   # noqa: E731
-        e0, i0, j0 = plan["first"]
-        _lib.check(L.mi355gs_align_init_apply(st, n, rec(e0, 0), 4, None, img(i0)), "align_init_apply")
-        _lib.check(L.mi355gs_align_init_apply(st, n, rec(e0, 1), 4, None, img(j0)), "align_init_apply")
-        for k, (e, side, i, j) in enumerate(plan["steps"]):
-            known, new = (i, j) if side == 0 else (j, i)
-            conf = (P.conf_i if side == 0 else P.conf_j)[e]
-            _lib.check(L.mi355gs_align_init_register(_lib.ptr(ws), st, 1, n, rec(e, side), None, 0, 4, img(known), None, 0, _lib.ptr(conf), None, 0,
-                                                     row(k), None), "align_init_register")
-            _lib.check(L.mi355gs_align_init_apply(st, n, rec(e, 1 - side), 4, row(k), img(new)), "align_init_apply")
+                continue
+            if host_focals is None:
+                host_focals = focals.cpu()                                   # the second synchronisation
+            focal = float(host_focals[focal_row[v]]) if v in focal_row else None
+            res = pnp_fn(pts3d[v].view(H, W, 3), focal, im_conf[v] > min_conf_thr)
+            if not res:
+                continue                                                     # the identity (init_im_poses.py:215-216)
+            focal, cam2world = res
+            c2w = torch.as_tensor(cam2world, dtype=torch.float32).reshape(4, 4).cpu()
+            pose_row[v] = n_steps + E + v
+            srt[pose_row[v]] = torch.cat([torch.ones(1), c2w[:3, :3].reshape(9), c2w[:3, 3], torch.zeros(3)]).to(dev)
+            focal_row[v] = len(focal_images) + v
+            focals[focal_row[v]] = float(focal)
 
-        # focals: one batch over the images that have a source record (they do not depend on the walk's results)
-        focals = torch.zeros(len(focal_images) + V, dtype=torch.float32, device=dev)   # the estimates, then pnp_fn's
-        _lib.check(L.mi355gs_align_init_focals(_lib.ptr(ws), st, len(focal_images), H, W, recs, _lib.ptr(src_idx), 4 * n, 4, _lib.ptr(focals)),
-                   "align_init_focals")
-
-        # pair poses: every edge's pred_i onto pts3d[i], weights conf_i (init_im_poses.py:109-113)
-        pw_pose = torch.empty(E, 8, dtype=torch.float32, device=dev)
-        _lib.check(L.mi355gs_align_init_register(_lib.ptr(ws), st, E, n, recs, _lib.ptr(pair_src), 4 * n, 4, _lib.ptr(pts3d), _lib.ptr(pair_tgt),
-                                                 3 * n, _lib.ptr(P.conf_i), None, n, row(n_steps), _lib.ptr(pw_pose)), "align_init_register")
-
-        if pnp_fn is not None:
-            im_conf, host_focals = P.im_conf(), None
-            for v in range(V):
-                if v in plan["pose_step"]:
-                    continue
-                if host_focals is None:
-                    host_focals = focals.cpu()                                   # the second synchronisation
-                focal = float(host_focals[focal_row[v]]) if v in focal_row else None
-                res = pnp_fn(pts3d[v].view(H, W, 3), focal, im_conf[v] > min_conf_thr)
-                if not res:
-                    continue                                                     # the identity (init_im_poses.py:215-216)
-                focal, cam2world = res
-                c2w = torch.as_tensor(cam2world, dtype=torch.float32).reshape(4, 4).cpu()
-                pose_row[v] = n_steps + E + v
-                srt[pose_row[v]] = torch.cat([torch.ones(1), c2w[:3, :3].reshape(9), c2w[:3, 3], torch.zeros(3)]).to(dev)
-                focal_row[v] = len(focal_images) + v
-                focals[focal_row[v]] = float(focal)
-
-        depth_log = torch.empty(V, n, dtype=torch.float32, device=dev)
-        im_pose = torch.empty(V, 7, dtype=torch.float32, device=dev)
-        focal_log = torch.empty(V, dtype=torch.float32, device=dev)
-        if pnp_fn is not None:
-            pose_row_d, focal_row_d = i32(pose_row), i32(focal_row.get(v, -1) for v in range(V))
-        mode = 2 if known_focal is not None else (1 if focal_avg else 0)
-        _lib.check(L.mi355gs_align_init_state(_lib.ptr(ws), st, V, E, H, W, 1 if P.flags & NORM_PW_SCALE else 0, P.base_scale, mode,
-                                              float(known_focal) if known_focal is not None else 0.0, _lib.ptr(srt), _lib.ptr(pose_row_d),
-                                              _lib.ptr(focals), _lib.ptr(focal_row_d), _lib.ptr(pw_pose), _lib.ptr(pts3d), _lib.ptr(depth_log),
-                                              _lib.ptr(im_pose), _lib.ptr(focal_log)), "align_init_state")
-        state = AlignState(P, depth_log, im_pose, focal_log, torch.zeros(V, 2, dtype=torch.float32, device=dev), pw_pose)
+    depth_log = torch.empty(V, n, dtype=torch.float32, device=dev)
+    im_pose = torch.empty(V, 7, dtype=torch.float32, device=dev)
+    focal_log = torch.empty(V, dtype=torch.float32, device=dev)
+    if pnp_fn is not None:
+        pose_row_d, focal_row_d = i32(pose_row), i32(focal_row.get(v, -1) for v in range(V))
+    mode = 2 if known_focal is not None else (1 if focal_avg else 0)
+    run("state", ws, _lib.STREAM, V, E, H, W, 1 if P.flags & NORM_PW_SCALE else 0, P.base_scale, mode,
+        float(known_focal) if known_focal is not None else 0.0, srt, pose_row_d, focals, focal_row_d, pw_pose, pts3d, depth_log, im_pose, focal_log)
+    state = AlignState(P, depth_log, im_pose, focal_log, torch.zeros(V, 2, dtype=torch.float32, device=dev), pw_pose)
     state.mst_edges, state.init_pts3d, state.focal_edge, state.edge_scores = plan["mst_edges"], pts3d.view(V, H, W, 3), dict(plan["focal_edge"]), scores
     state.init_focals = focals[:len(focal_images)]   # the per-image Weiszfeld estimates, in the order of sorted(focal_edge)
     return state
@@ -528,8 +501,6 @@ def gradients(problem: AlignProblem, state: AlignState) -> dict:
     dev = problem.device
     g = {k: torch.empty_like(getattr(state, k)) for k in ("depth_log", "im_pose", "focal_log", "pw_pose")}
     loss = torch.empty(1, dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().mi355gs_align_grad(problem._handle, _lib.stream_ptr(dev), *state._state_ptrs(), *[_lib.ptr(g[k]) for k in g],
-                                                 _lib.ptr(loss)), "align_grad")
+    _lib.call(dev, "align_grad", problem._h, _lib.STREAM, *state._state_ptrs(), *g.values(), loss)
     g["loss"] = loss
     return g

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._frames import device_of, to_device
 
 MAX_VIEWS = 256                    # include/mi355gs.h: V of one call
 MAX_ELEMENTS = 2 ** 31 - 1         # ... and V H W
@@ -34,28 +35,6 @@ def _as_tensor(x, dtype, what):
     if t.dtype != dtype:
         raise ValueError(f"{what} must be {dtype}, got {t.dtype}")
     return t
-
-
-def _device_of(tensors):
-    """The device the stage runs on: the one device of the CUDA tensors among the arguments, else the current one (host tensors
-    then take one copy each).  Under the emulator's test mode CPU tensors are used where they are; otherwise a missing GPU is an
-    error (there is no CPU fallback)."""
-    cuda = {t.device for t in tensors if t.is_cuda}
-    if len(cuda) > 1:
-        raise ValueError(f"tensors on different devices: {sorted(str(d) for d in cuda)}")
-    if cuda:
-        return cuda.pop()
-    if _lib._TEST_MODE:
-        return torch.device("cpu")
-    if not torch.cuda.is_available():
-        raise RuntimeError("instantsplat_amd operators run on the GPU only (got a CPU tensor; there is no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _on(t: torch.Tensor, dev) -> torch.Tensor:
-    if t.device != dev:
-        t = t.to(dev, non_blocking=t.is_pinned())
-    return t if t.is_contiguous() else t.contiguous()
 
 
 def _check_maps(depthmaps, pointmaps=None, confidences=None, images=None, intrinsics=None, w2c=None):
@@ -85,28 +64,19 @@ def _check_order(order, V):
 def _pointmap_stats(depthmaps, confidences, dev):
     """-> (stats float64 [V,3] on the device: min depth, max depth, confidence sum; overlap uint8 [V,H,W], cleared)"""
     V, H, W = (int(s) for s in depthmaps.shape)
-    L = _lib.lib()
-    nbytes = int(L.mi355gs_pointmap_stats_scratch_bytes(V, H, W))
-    if not nbytes:
-        raise ValueError(f"mi355gs_pointmap_stats does not take {V} views of {H} x {W} (include/mi355gs.h: the limits)")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = _lib.scratch(dev, "pointmap_stats_scratch_bytes", V, H, W,
+                           what=f"mi355gs_pointmap_stats does not take {V} views of {H} x {W} (include/mi355gs.h: the limits)")
     stats = torch.empty(V, 3, dtype=torch.float64, device=dev)
     overlap = torch.empty(V, H, W, dtype=torch.uint8, device=dev)   # cleared by the statistics pass
-    with _lib.on_device(dev):
-        _lib.check(L.mi355gs_pointmap_stats(_lib.stream_ptr(dev), V, H, W, _lib.ptr(depthmaps), _lib.ptr(confidences), _lib.ptr(overlap),
-                                            _lib.ptr(scratch), _lib.ptr(stats)), "pointmap_stats")
+    _lib.call(dev, "pointmap_stats", _lib.STREAM, V, H, W, depthmaps, confidences, overlap, scratch, stats)
     return stats, overlap
 
 
 def _covis_masks(order, pointmaps, depthmaps, intrinsics, w2c, stats, depth_threshold, overlap, dev):
     import ctypes
     V, H, W = (int(s) for s in depthmaps.shape)
-    L = _lib.lib()
-    host_order = (ctypes.c_int32 * V)(*order)
-    with _lib.on_device(dev):
-        _lib.check(L.mi355gs_covis_masks(_lib.stream_ptr(dev), V, H, W, host_order, _lib.ptr(pointmaps), _lib.ptr(depthmaps),
-                                         _lib.ptr(intrinsics), _lib.ptr(w2c), _lib.ptr(stats), float(depth_threshold), _lib.ptr(overlap)),
-                   "covis_masks")
+    _lib.call(dev, "covis_masks", _lib.STREAM, V, H, W, (ctypes.c_int32 * V)(*order), pointmaps, depthmaps, intrinsics, w2c, stats,
+              float(depth_threshold), overlap)
 
 
 def co_visibility_masks(order, depthmaps, pointmaps, intrinsics, w2c, depth_threshold=0.1) -> torch.Tensor:
@@ -121,8 +91,8 @@ def co_visibility_masks(order, depthmaps, pointmaps, intrinsics, w2c, depth_thre
     intrinsics, w2c = _as_tensor(intrinsics, torch.float32, "intrinsics"), _as_tensor(w2c, torch.float32, "w2c")
     V, H, W = _check_maps(depthmaps, pointmaps=pointmaps, intrinsics=intrinsics, w2c=w2c)
     order = _check_order(order, V)
-    dev = _device_of((depthmaps, pointmaps, intrinsics, w2c))
-    depthmaps, pointmaps, intrinsics, w2c = (_on(t, dev) for t in (depthmaps, pointmaps, intrinsics, w2c))
+    dev = device_of((depthmaps, pointmaps, intrinsics, w2c))
+    depthmaps, pointmaps, intrinsics, w2c = (to_device(t, dev) for t in (depthmaps, pointmaps, intrinsics, w2c))
     stats, overlap = _pointmap_stats(depthmaps, depthmaps, dev)   # (the confidence sums are not needed here)
     _covis_masks(order, pointmaps, depthmaps, intrinsics, w2c, stats, depth_threshold, overlap, dev)
     return overlap.view(torch.bool)
@@ -150,23 +120,19 @@ def compact_pointmaps(pointmaps, images, confidences, overlap=None):
     if overlap is not None:
         if not isinstance(overlap, torch.Tensor) or overlap.dtype not in (torch.bool, torch.uint8) or int(overlap.numel()) != n:
             raise ValueError("overlap must be a bool or uint8 tensor with one element per point")
-    dev = _device_of((pointmaps, images, confidences) + ((overlap,) if overlap is not None else ()))
-    pointmaps, images, confidences = (_on(t, dev) for t in (pointmaps, images, confidences))
+    dev = device_of((pointmaps, images, confidences) + ((overlap,) if overlap is not None else ()))
+    pointmaps, images, confidences = (to_device(t, dev) for t in (pointmaps, images, confidences))
     if overlap is not None:
-        overlap = _on(overlap, dev)
-    L = _lib.lib()
-    scratch = torch.empty(int(L.mi355gs_compact_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+        overlap = to_device(overlap, dev)
+    scratch = _lib.scratch(dev, "compact_scratch_bytes", n, what=f"mi355gs_compact_pointmaps does not take {n} elements")
     points = torch.empty(n, 3, dtype=torch.float32, device=dev)
     rgb8 = torch.empty(n, 3, dtype=torch.uint8, device=dev)
     conf = torch.empty(n, 1, dtype=torch.float32, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     word = torch.full((1,), -1, dtype=torch.int32, pin_memory=(dev.type == "cuda"))
-    with _lib.on_device(dev):
-        _lib.check(L.mi355gs_compact_pointmaps(_lib.stream_ptr(dev), n, _lib.ptr(overlap), _lib.ptr(pointmaps), _lib.ptr(images),
-                                               _lib.ptr(confidences), _lib.ptr(scratch), _lib.ptr(points), _lib.ptr(rgb8), _lib.ptr(conf),
-                                               _lib.ptr(count), _lib.ptr(word)), "compact_pointmaps")
-        if dev.type == "cuda":
-            torch.cuda.current_stream(dev).synchronize()
+    _lib.call(dev, "compact_pointmaps", _lib.STREAM, n, overlap, pointmaps, images, confidences, scratch, points, rgb8, conf, count, word)
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()
     M = int(word[0])
     if not 0 <= M <= n:
         raise RuntimeError(f"compact_pointmaps: the count word holds {M} for {n} elements")
@@ -243,9 +209,9 @@ def init_from_pointmaps(source_path, n_views, images, pointmaps, depthmaps, conf
     n_test = int(n_test)
     if n_test > 0 and (test_names is None or len(test_names) != n_test):
         raise ValueError(f"n_test = {n_test} needs {n_test} test_names")
-    dev = _device_of((images, pointmaps, depthmaps, confidences, intrinsics, w2c))
+    dev = device_of((images, pointmaps, depthmaps, confidences, intrinsics, w2c))
     w2c_host = w2c.detach().cpu().numpy()
-    images, pointmaps, depthmaps, confidences, intrinsics, w2c = (_on(t, dev) for t in (images, pointmaps, depthmaps, confidences, intrinsics, w2c))
+    images, pointmaps, depthmaps, confidences, intrinsics, w2c = (to_device(t, dev) for t in (images, pointmaps, depthmaps, confidences, intrinsics, w2c))
 
     stats, overlap = _pointmap_stats(depthmaps, confidences, dev)
     order = [int(o) for o in confidence_ranking(stats[:, 2].cpu().numpy(), H, W)] if conf_aware_ranking else list(range(V))

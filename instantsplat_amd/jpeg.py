@@ -13,7 +13,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 MAX_FRAMES_PER_CALL = 65535   # include/mi355gs.h: N of one mi355gs_jpeg_rgb8 call (a grid dimension)
 HEADER_BYTES = 1024           # room per file for its 629 bytes of header, the restart markers and EOI in the default capacity
@@ -35,10 +35,6 @@ def quant_tables(quality) -> np.ndarray:
     return np.clip((base * s + 50) // 100, 1, 255).astype(np.uint8)
 
 
-def _call_sizes(L, n, H, W, sub):
-    return int(L.mi355gs_jpeg_rgb8_scratch_bytes(n, H, W, sub)), int(L.mi355gs_jpeg_rgb8_stream_bytes(n, H, W, sub))
-
-
 def encode_jpeg_rgb8(frames: torch.Tensor, quality=90, subsampling: str = "4:2:0", qtables=None, capacity: int | None = None,
                      max_call_bytes: int = 1 << 30) -> dict:
     """frames: contiguous uint8 [N,H,W,3] (or [H,W,3]) on the device -> dict(stream: uint8 host tensor holding the N files back to
@@ -53,13 +49,7 @@ def encode_jpeg_rgb8(frames: torch.Tensor, quality=90, subsampling: str = "4:2:0
     N is split into library calls whose scratch and output buffers together stay under max_call_bytes (one frame per call at
     least); per call `offsets` is read back once and only the files' bytes are copied to the host.
     Raises ValueError for anything but a contiguous uint8 device tensor of that shape, or sizes beyond the library's limits."""
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-        raise ValueError("encode_jpeg_rgb8 takes a uint8 [N,H,W,3] or [H,W,3] tensor, got "
-                         f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)} {getattr(frames, 'dtype', '')}")
-    if not frames.is_cuda and not _lib._TEST_MODE:
-        raise ValueError("encode_jpeg_rgb8 encodes on the GPU only (got a CPU tensor; there is no CPU fallback): pass frames.to(device)")
-    if not frames.is_contiguous():
-        raise ValueError("encode_jpeg_rgb8 takes a contiguous tensor")
+    frames, N, H, W = _frames.check_frames("encode_jpeg_rgb8", frames)
     if not isinstance(subsampling, str) or subsampling not in SUBSAMPLINGS:
         raise ValueError(f'subsampling must be "4:2:0" or "4:4:4", got {subsampling!r}')
     sub = SUBSAMPLINGS[subsampling]
@@ -72,70 +62,46 @@ def encode_jpeg_rgb8(frames: torch.Tensor, quality=90, subsampling: str = "4:2:0
     qt = np.ascontiguousarray(qt, dtype=np.uint8)
     if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0):
         raise ValueError(f"capacity must be a non-negative integer or None, got {capacity!r}")
-    if frames.dim() == 3:
-        frames = frames[None]
-    N, H, W = (int(s) for s in frames.shape[:3])
-    if H <= 0 or W <= 0:
-        raise ValueError(f"empty frames: {H} x {W}")
     if N == 0:
         return dict(stream=torch.empty(0, dtype=torch.uint8), offsets=np.zeros(1, np.int64))
     L = _lib.lib()
-    scratch1, stream1 = _call_sizes(L, 1, H, W, sub)
-    if not scratch1:
+    scratch_bytes = lambda n: int(L.mi355gs_jpeg_rgb8_scratch_bytes(n, H, W, sub))
+    stream_bytes = lambda n: int(L.mi355gs_jpeg_rgb8_stream_bytes(n, H, W, sub))
+    if not scratch_bytes(1):
         raise ValueError(f"mi355gs_jpeg_rgb8 does not take frames of {H} x {W} (include/mi355gs.h: the limits)")
     frame_bytes = 3 * H * W
-    room = lambda n: min(n * (frame_bytes // 2 + HEADER_BYTES), _call_sizes(L, n, H, W, sub)[1]) if capacity is None else int(capacity)
-    fits = lambda n: _call_sizes(L, n, H, W, sub)[0] + room(n) + 8 * (n + 1) <= max_call_bytes
-    cap = min(MAX_FRAMES_PER_CALL, N)
-    per_call = max(1, min(cap, int(max_call_bytes) // (scratch1 + room(1) + 8)))   # an estimate: the buffers are padded
-    while per_call > 1 and not fits(per_call):
-        per_call -= 1
-    while per_call < cap and fits(per_call + 1):
-        per_call += 1
+    room = lambda n: min(n * (frame_bytes // 2 + HEADER_BYTES), stream_bytes(n)) if capacity is None else int(capacity)
+    per_call = _frames.frames_per_call(lambda n: scratch_bytes(n) + room(n) + 8 * (n + 1) <= max_call_bytes, min(MAX_FRAMES_PER_CALL, N),
+                                       int(max_call_bytes) // (scratch_bytes(1) + room(1) + 8))
     dev = frames.device
-    parts, offsets, base = [], [np.zeros(1, np.int64)], 0
 
     def call(first, n, scratch, out, out_bytes, offs):
-        _lib.check(L.mi355gs_jpeg_rgb8(_lib.stream_ptr(dev), n, H, W, sub, qt.ctypes.data, frames.data_ptr() + first * frame_bytes,
-                                       _lib.ptr(scratch), _lib.ptr(out), out_bytes, _lib.ptr(offs)), "jpeg_rgb8")
+        _lib.call(dev, "jpeg_rgb8", _lib.STREAM, n, H, W, sub, qt.ctypes.data, frames.data_ptr() + first * frame_bytes, scratch, out, out_bytes,
+                  offs)
         return offs.cpu().numpy().copy()   # the call's one read-back; the copies below take only the bytes the files have
 
-    with _lib.on_device(dev):
-        scratch = out = offs = None
-        out_bytes = 0
-        for first in range(0, N, per_call):
-            n = min(per_call, N - first)
-            if scratch is None or n != per_call:
-                nscratch = _call_sizes(L, n, H, W, sub)[0]
-                if not nscratch:
-                    raise ValueError(f"mi355gs_jpeg_rgb8 does not take {n} frames of {H} x {W} (include/mi355gs.h: the limits)")
-                scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
-                out_bytes = room(n)
-                out = torch.empty(max(out_bytes, 1), dtype=torch.uint8, device=dev)   # (an empty tensor has no address)
-                offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            o = call(first, n, scratch, out, out_bytes, offs)
-            done = int(np.searchsorted(o, out_bytes, side="right")) - 1   # files 0 .. done-1 fitted: offsets[i+1] <= capacity
-            files = out[:int(o[done])].cpu()
-            parts.append(files if out.is_cuda else files.clone())   # (the buffers are reused by the next call)
-            if done < n:   # the rest once more, into exactly their bytes
-                rest = torch.empty(int(o[n] - o[done]), dtype=torch.uint8, device=dev)
-                o2 = call(first + done, n - done, scratch, rest, rest.numel(), offs[:n - done + 1])
-                if int(o2[-1]) != rest.numel():
-                    raise RuntimeError("mi355gs_jpeg_rgb8 reported different sizes for the same frames")
-                parts.append(rest.cpu())
-            offsets.append(o[1:] + base)
-            base += int(o[-1])
-    return dict(stream=parts[0] if len(parts) == 1 else torch.cat(parts), offsets=np.concatenate(offsets))
+    def buffers(n):
+        scratch = _lib.scratch(dev, "jpeg_rgb8_scratch_bytes", n, H, W, sub,
+                               what=f"mi355gs_jpeg_rgb8 does not take {n} frames of {H} x {W} (include/mi355gs.h: the limits)")
+        out_bytes = room(n)
+        return (scratch, torch.empty(max(out_bytes, 1), dtype=torch.uint8, device=dev),   # (an empty tensor has no address)
+                out_bytes, torch.empty(n + 1, dtype=torch.int64, device=dev))
+
+    def encode_call(first, n, scratch, out, out_bytes, offs):
+        o = call(first, n, scratch, out, out_bytes, offs)
+        done = int(np.searchsorted(o, out_bytes, side="right")) - 1   # files 0 .. done-1 fitted: offsets[i+1] <= capacity
+        files = [_frames.host_bytes(out, int(o[done]))]
+        if done < n:   # the rest once more, into exactly their bytes
+            rest = torch.empty(int(o[n] - o[done]), dtype=torch.uint8, device=dev)
+            o2 = call(first + done, n - done, scratch, rest, rest.numel(), offs[:n - done + 1])
+            if int(o2[-1]) != rest.numel():
+                raise RuntimeError("mi355gs_jpeg_rgb8 reported different sizes for the same frames")
+            files.append(rest.cpu())
+        return o, files
+
+    return _frames.encode_in_calls(N, per_call, buffers, encode_call)
 
 
 def write_jpeg_files(paths: Sequence[str], frames: torch.Tensor, **kw) -> None:
     """Encode frames (as `encode_jpeg_rgb8` takes them) and write file i to paths[i] with one write each."""
-    paths = list(paths)
-    n = 1 if isinstance(frames, torch.Tensor) and frames.dim() == 3 else len(frames)
-    if len(paths) != n:
-        raise ValueError(f"{len(paths)} paths for {n} frames")
-    enc = encode_jpeg_rgb8(frames, **kw)
-    data, offsets = memoryview(enc["stream"].numpy()), enc["offsets"]
-    for i, path in enumerate(paths):
-        with open(path, "wb") as fh:
-            fh.write(data[int(offsets[i]):int(offsets[i + 1])])
+    _frames.write_stream_files(paths, frames, encode_jpeg_rgb8, **kw)

@@ -15,8 +15,7 @@ import re
 import numpy as np
 import torch
 
-from . import _lib
-from .metrics import _to_scoring_device
+from . import _frames, _lib
 
 CONV_LAYERS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)   # torchvision vgg16().features indices of the convolutions
 BLOCK_CONVS = (2, 2, 3, 3, 3)
@@ -78,11 +77,7 @@ class LpipsVGG:
         self.channels = tuple(channels)
         self._channels_c = (ctypes.c_int * 5)(*channels)
         blob = torch.cat(parts).contiguous()
-        if device is None and not _lib._TEST_MODE:
-            if not torch.cuda.is_available():
-                raise RuntimeError("instantsplat_amd operators run on the GPU only (there is no CPU fallback)")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.blob = blob if device is None else blob.to(device)
+        self.blob = blob.to(_frames.device_of((), default=device))
 
     @classmethod
     def from_files(cls, vgg_path, lin_path, device=None):
@@ -98,38 +93,21 @@ class LpipsVGG:
         of 2 n H W x the widest block) stays under `scratch_budget` bytes — at least one pair per call — and both results come
         back in ONE read-back.  -> dict of host arrays: lpips float32 [N], taps float32 [N,5] (the five layers' terms).
         Raises ValueError for anything but two uint8 [N,H,W,3] tensors of one shape with H, W >= 16."""
-        for t in (renders, gts):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-                raise ValueError("lpips_rgb8 takes two uint8 [N,H,W,3] tensors, got "
-                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} {getattr(t, 'dtype', '')}")
-        if renders.shape != gts.shape:
-            raise ValueError(f"renders {tuple(renders.shape)} and ground truth {tuple(gts.shape)} differ in shape")
-        N, H, W = (int(s) for s in renders.shape[:3])
+        N, H, W = _frames.check_pair("lpips_rgb8", renders, gts)
         if N == 0:
             return dict(lpips=np.zeros(0, np.float32), taps=np.zeros((0, 5), np.float32))
         if H < 16 or W < 16:
             raise ValueError(f"frames of {H} x {W}: the fifth block needs at least 16 x 16")
-        cuda = [t.device for t in (renders, gts) if t.is_cuda]
-        if len(cuda) == 2 and cuda[0] != cuda[1]:
-            raise ValueError(f"frames on different devices: {cuda[0]} vs {cuda[1]}")
-        want = cuda[0] if cuda else (self.blob.device if self.blob.is_cuda else None)
-        a = _to_scoring_device(renders, want)
-        b = _to_scoring_device(gts, want)
-        dev = _lib.require_device(a, b, self.blob)
-        one = self._scratch_bytes(1, H, W)
-        if not one:
+        a, b, dev = _frames.pair_on_device(renders, gts, self.blob, default=self.blob.device if self.blob.is_cuda else None)
+        if not self._scratch_bytes(1, H, W):
             raise ValueError(f"mi355gs_lpips_vgg_rgb8 does not take frames of {H} x {W} (include/mi355gs.h: the limits)")
-        n = max(1, min(N, int(scratch_budget) // one))
-        while n > 1 and not 0 < self._scratch_bytes(n, H, W) <= scratch_budget:
-            n -= 1
-        L = _lib.lib()
+        n = _frames.frames_per_call(lambda n: 0 < self._scratch_bytes(n, H, W) <= scratch_budget, N,
+                                    int(scratch_budget) // self._scratch_bytes(1, H, W))
         out = torch.empty(6 * N, dtype=torch.float32, device=dev)   # lpips [N] then taps [N][5]: one block, one read-back
-        scratch = torch.empty(self._scratch_bytes(n, H, W), dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            for first in range(0, N, n):
-                m = min(n, N - first)
-                _lib.check(L.mi355gs_lpips_vgg_rgb8(_lib.stream_ptr(dev), m, H, W, _lib.ptr(a[first:first + m]), _lib.ptr(b[first:first + m]),
-                                                    self._channels_c, _lib.ptr(self.blob), _lib.ptr(scratch), out.data_ptr() + 4 * first,
-                                                    out.data_ptr() + 4 * (N + 5 * first)), "lpips_vgg_rgb8")
+        scratch = _lib.scratch(dev, "lpips_vgg_scratch_bytes", n, H, W, self._channels_c, what=None)
+        for first in range(0, N, n):
+            m = min(n, N - first)
+            _lib.call(dev, "lpips_vgg_rgb8", _lib.STREAM, m, H, W, a[first:first + m], b[first:first + m], self._channels_c, self.blob, scratch,
+                      out.data_ptr() + 4 * first, out.data_ptr() + 4 * (N + 5 * first))
         host = out.cpu().numpy()   # the one read-back (it also orders the launches before the scratch block is released)
         return dict(lpips=host[:N].copy(), taps=host[N:].reshape(N, 5).copy())

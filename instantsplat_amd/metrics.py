@@ -19,25 +19,13 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 MAX_FRAMES_PER_CALL = 65535   # include/mi355gs.h: N of one mi355gs_metrics_rgb8 call (a grid dimension)
 
 
 def _empty():
     return dict(sq_sum=np.zeros(0, np.int64), mse=np.zeros(0, np.float64), psnr=np.zeros(0, np.float64), ssim=np.zeros(0, np.float32))
-
-
-def _to_scoring_device(t: torch.Tensor, dev):
-    """Device tensors stay; host tensors (pinned or not) take ONE host-to-device copy.  Under the emulator's test mode CPU tensors
-    are scored where they are; otherwise a missing GPU is an error (there is no CPU fallback)."""
-    if t.is_cuda or _lib._TEST_MODE:
-        return t if t.is_contiguous() else t.contiguous()
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("instantsplat_amd operators run on the GPU only (got a CPU tensor; there is no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return t.contiguous().to(dev, non_blocking=t.is_pinned())
 
 
 def image_metrics_rgb8(renders: torch.Tensor, gts: torch.Tensor) -> dict:
@@ -56,35 +44,19 @@ def image_metrics_rgb8(renders: torch.Tensor, gts: torch.Tensor) -> dict:
     was seen on the golden pairs: 4.7e-6 dB).  Here the sum is an exact integer and everything after it is float64 on the host, so
     the value is at least as close to the true PSNR as the reference's.
     Raises ValueError for anything but two uint8 [N,H,W,3] tensors of one shape, or sizes beyond the library's limits."""
-    for t in (renders, gts):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3:
-            raise ValueError("image_metrics_rgb8 takes two uint8 [N,H,W,3] tensors, got "
-                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)} {getattr(t, 'dtype', '')}")
-    if renders.shape != gts.shape:
-        raise ValueError(f"renders {tuple(renders.shape)} and ground truth {tuple(gts.shape)} differ in shape")
-    N, H, W = (int(s) for s in renders.shape[:3])
+    N, H, W = _frames.check_pair("image_metrics_rgb8", renders, gts)
     if N == 0:
         return _empty()
     if H <= 0 or W <= 0:
         raise ValueError(f"empty frames: {H} x {W}")
-    cuda = [t.device for t in (renders, gts) if t.is_cuda]
-    if len(cuda) == 2 and cuda[0] != cuda[1]:
-        raise ValueError(f"frames on different devices: {cuda[0]} vs {cuda[1]}")
-    a = _to_scoring_device(renders, cuda[0] if cuda else None)
-    b = _to_scoring_device(gts, a.device if a.is_cuda else None)
-    dev = _lib.require_device(a, b)
-    L = _lib.lib()
+    a, b, dev = _frames.pair_on_device(renders, gts)
     out = torch.empty(12 * N, dtype=torch.uint8, device=dev)   # int64 [N] then float32 [N]: one block, one read-back
-    with _lib.on_device(dev):
-        for first in range(0, N, MAX_FRAMES_PER_CALL):
-            n = min(MAX_FRAMES_PER_CALL, N - first)
-            nbytes = int(L.mi355gs_metrics_rgb8_scratch_bytes(n, H, W))
-            if not nbytes:
-                raise ValueError(f"mi355gs_metrics_rgb8 does not take {n} frames of {H} x {W} (include/mi355gs.h: the limits)")
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.mi355gs_metrics_rgb8(_lib.stream_ptr(dev), n, H, W, _lib.ptr(a[first:first + n]), _lib.ptr(b[first:first + n]),
-                                              _lib.ptr(scratch), out.data_ptr() + 8 * first, out.data_ptr() + 8 * N + 4 * first),
-                       "metrics_rgb8")
+    for first in range(0, N, MAX_FRAMES_PER_CALL):
+        n = min(MAX_FRAMES_PER_CALL, N - first)
+        scratch = _lib.scratch(dev, "metrics_rgb8_scratch_bytes", n, H, W,
+                               what=f"mi355gs_metrics_rgb8 does not take {n} frames of {H} x {W} (include/mi355gs.h: the limits)")
+        _lib.call(dev, "metrics_rgb8", _lib.STREAM, n, H, W, a[first:first + n], b[first:first + n], scratch, out.data_ptr() + 8 * first,
+                  out.data_ptr() + 8 * N + 4 * first)
     host = out.cpu().numpy()   # the one read-back (it also orders the launches before the scratch blocks are released)
     sq = host[:8 * N].view(np.int64).copy()
     ssim = host[8 * N:].view(np.float32).copy()

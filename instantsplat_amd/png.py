@@ -15,13 +15,9 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 MAX_FRAMES_PER_CALL = 65535   # include/mi355gs.h: N of one mi355gs_png_rgb8 call (a grid dimension)
-
-
-def _call_sizes(L, n, H, W, R):
-    return int(L.mi355gs_png_rgb8_scratch_bytes(n, H, W, R)), int(L.mi355gs_png_rgb8_stream_bytes(n, H, W, R))
 
 
 def encode_png_rgb8(frames: torch.Tensor, rows_per_block: int | None = None, max_call_bytes: int = 1 << 30) -> dict:
@@ -32,67 +28,36 @@ def encode_png_rgb8(frames: torch.Tensor, rows_per_block: int | None = None, max
     calls whose scratch and output buffers together stay under max_call_bytes (one frame per call at least); per call `offsets`
     is read back once and only the used prefix of the output is copied to the host.
     Raises ValueError for anything but a contiguous uint8 device tensor of that shape, or sizes beyond the library's limits."""
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
-        raise ValueError("encode_png_rgb8 takes a uint8 [N,H,W,3] or [H,W,3] tensor, got "
-                         f"{tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)} {getattr(frames, 'dtype', '')}")
-    if not frames.is_cuda and not _lib._TEST_MODE:
-        raise ValueError("encode_png_rgb8 encodes on the GPU only (got a CPU tensor; there is no CPU fallback): pass frames.to(device)")
-    if not frames.is_contiguous():
-        raise ValueError("encode_png_rgb8 takes a contiguous tensor")
-    if frames.dim() == 3:
-        frames = frames[None]
-    N, H, W = (int(s) for s in frames.shape[:3])
-    if H <= 0 or W <= 0:
-        raise ValueError(f"empty frames: {H} x {W}")
+    frames, N, H, W = _frames.check_frames("encode_png_rgb8", frames)
     R = 0 if rows_per_block is None else int(rows_per_block)
     if rows_per_block is not None and R < 1:
         raise ValueError(f"rows_per_block must be at least 1, got {rows_per_block}")
     if N == 0:
         return dict(stream=torch.empty(0, dtype=torch.uint8), offsets=np.zeros(1, np.int64))
     L = _lib.lib()
-    scratch1, stream1 = _call_sizes(L, 1, H, W, R)
+    sizes = lambda n: (int(L.mi355gs_png_rgb8_scratch_bytes(n, H, W, R)), int(L.mi355gs_png_rgb8_stream_bytes(n, H, W, R)))
+    scratch1, stream1 = sizes(1)
     if not scratch1:
         raise ValueError(f"mi355gs_png_rgb8 does not take frames of {H} x {W} with rows_per_block = {rows_per_block} "
                          "(include/mi355gs.h: the limits)")
-    fits = lambda n: sum(_call_sizes(L, n, H, W, R)) + 8 * (n + 1) <= max_call_bytes
-    cap = min(MAX_FRAMES_PER_CALL, N)
-    per_call = max(1, min(cap, int(max_call_bytes) // (scratch1 + stream1 + 8)))   # an estimate: the buffers are padded
-    while per_call > 1 and not fits(per_call):
-        per_call -= 1
-    while per_call < cap and fits(per_call + 1):
-        per_call += 1
+    per_call = _frames.frames_per_call(lambda n: sum(sizes(n)) + 8 * (n + 1) <= max_call_bytes, min(MAX_FRAMES_PER_CALL, N),
+                                       int(max_call_bytes) // (scratch1 + stream1 + 8))
     dev = frames.device
     frame_bytes = 3 * H * W
-    parts, offsets, base = [], [np.zeros(1, np.int64)], 0
-    with _lib.on_device(dev):
-        scratch = out = offs = None
-        for first in range(0, N, per_call):
-            n = min(per_call, N - first)
-            if scratch is None or n != per_call:
-                nscratch, nstream = _call_sizes(L, n, H, W, R)
-                if not nscratch:
-                    raise ValueError(f"mi355gs_png_rgb8 does not take {n} frames of {H} x {W} (include/mi355gs.h: the limits)")
-                scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
-                out = torch.empty(nstream, dtype=torch.uint8, device=dev)
-                offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            _lib.check(L.mi355gs_png_rgb8(_lib.stream_ptr(dev), n, H, W, R, frames.data_ptr() + first * frame_bytes, _lib.ptr(scratch),
-                                          _lib.ptr(out), _lib.ptr(offs)), "png_rgb8")
-            o = offs.cpu().numpy()   # the call's one read-back; the copy below takes only the bytes the files have
-            files = out[:int(o[-1])].cpu()
-            parts.append(files if out.is_cuda else files.clone())   # (the buffers are reused by the next call)
-            offsets.append(o[1:] + base)
-            base += int(o[-1])
-    return dict(stream=parts[0] if len(parts) == 1 else torch.cat(parts), offsets=np.concatenate(offsets))
+
+    def buffers(n):
+        scratch = _lib.scratch(dev, "png_rgb8_scratch_bytes", n, H, W, R,
+                               what=f"mi355gs_png_rgb8 does not take {n} frames of {H} x {W} (include/mi355gs.h: the limits)")
+        return (scratch, torch.empty(sizes(n)[1], dtype=torch.uint8, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev))
+
+    def encode_call(first, n, scratch, out, offs):
+        _lib.call(dev, "png_rgb8", _lib.STREAM, n, H, W, R, frames.data_ptr() + first * frame_bytes, scratch, out, offs)
+        o = offs.cpu().numpy()   # the call's one read-back; the copy below takes only the bytes the files have
+        return o, [_frames.host_bytes(out, int(o[-1]))]
+
+    return _frames.encode_in_calls(N, per_call, buffers, encode_call)
 
 
 def write_png_files(paths: Sequence[str], frames: torch.Tensor, **kw) -> None:
     """Encode frames (as `encode_png_rgb8` takes them) and write file i to paths[i] with one write each."""
-    paths = list(paths)
-    n = 1 if isinstance(frames, torch.Tensor) and frames.dim() == 3 else len(frames)
-    if len(paths) != n:
-        raise ValueError(f"{len(paths)} paths for {n} frames")
-    enc = encode_png_rgb8(frames, **kw)
-    data, offsets = memoryview(enc["stream"].numpy()), enc["offsets"]
-    for i, path in enumerate(paths):
-        with open(path, "wb") as fh:
-            fh.write(data[int(offsets[i]):int(offsets[i + 1])])
+    _frames.write_stream_files(paths, frames, encode_png_rgb8, **kw)

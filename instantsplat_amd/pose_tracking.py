@@ -9,8 +9,6 @@ seven pose gradients on the device, so one tracking iteration is ~15 kernel laun
 """
 from __future__ import annotations
 
-import ctypes
-import math
 import os
 import time
 from typing import List
@@ -20,6 +18,7 @@ import torch
 from . import _lib
 from .diff_gaussian_rasterization import BinningPolicy
 from .gaussian_renderer import render
+from .handles import FrozenSceneHandle
 from .pose_utils import get_tensor_from_camera
 
 
@@ -99,53 +98,16 @@ def tracking_schedule(num_iter: int, dev) -> torch.Tensor:
     return tab
 
 
-class FusedPoseTracker:
+class FusedPoseTracker(FrozenSceneHandle):
     """Handle of mi355gs_tracker_*: the frozen Gaussians' raw parameters, one image size and an instance capacity."""
-
-    def __init__(self, gaussians, W: int, H: int, capacity: int):
-        g = gaussians
-        self.params = [t.detach() for t in (g._xyz, g._features_dc, g._features_rest, g._opacity, g._scaling, g._rotation)]
-        dev = _lib.require_device(*self.params)
-        P = int(self.params[0].shape[0])
-        M = 1 + int(self.params[2].shape[1]) if self.params[2].dim() == 3 else 1
-        shapes = ((P, 3), (P, 1, 3), (P, M - 1, 3), (P, 1), (P, 3), (P, 4))
-        for t, shape in zip(self.params, shapes):   # the library indexes raw pointers with these shapes
-            if t.dtype != torch.float32 or tuple(t.shape) != shape:
-                raise ValueError(f"fused pose tracking needs float32 parameters of shape {shape}, got {tuple(t.shape)} {t.dtype}")
-        L = _lib.lib()
-        self.dev, self.P, self.M, self.W, self.H, self.capacity = dev, P, M, int(W), int(H), int(capacity)
-        nbytes = L.mi355gs_tracker_workspace_bytes(P, self.W, self.H, self.capacity)
-        if not nbytes:
-            raise ValueError("mi355gs_tracker_workspace_bytes rejected the sizes")
-        self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        self.handle = L.mi355gs_tracker_create(P, M, self.W, self.H, self.capacity, *[_lib.ptr(t) for t in self.params],
-                                               _lib.ptr(self.workspace))
-        if not self.handle:
-            raise RuntimeError("mi355gs_tracker_create failed")
-
-    def close(self):
-        handle, self.handle = getattr(self, "handle", None), None
-        if handle:
-            try:
-                _lib.lib().mi355gs_tracker_destroy(ctypes.c_void_p(handle))
-            except Exception:  # interpreter shutdown
-                pass
-
-    __del__ = close
-
-    @staticmethod
-    def _camera(view, dev):
-        proj = view.projection_matrix.to(dev).float().contiguous()
-        return proj, math.tan(view.FoVx * 0.5), math.tan(view.FoVy * 0.5)
+    prefix, phrase = "tracker", "fused pose tracking"
 
     def count(self, view, sh_degree: int, pose: torch.Tensor) -> int:
         """Exact instance count of the view at `pose` (one blocking read)."""
         proj, tx, ty = self._camera(view, self.dev)
         pose = pose.detach().to(self.dev).float().contiguous()
         out = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        with _lib.on_device(self.dev):
-            _lib.check(_lib.lib().mi355gs_tracker_count(ctypes.c_void_p(self.handle), _lib.stream_ptr(self.dev), int(sh_degree),
-                                                        _lib.ptr(proj), tx, ty, _lib.ptr(pose), _lib.ptr(out)), "tracker_count")
+        _lib.call(self.dev, "tracker_count", self._h, _lib.STREAM, int(sh_degree), proj, tx, ty, pose, out)
         return int(out[0])
 
     @staticmethod
@@ -175,11 +137,8 @@ class FusedPoseTracker:
             if t is not None and (t.numel() != n * num_iter or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
                 raise ValueError("traces need float32 [num_iter, 7] / [num_iter] on the tracker's device")
         self._keep = (proj, gt, bg, sched)   # alive until the enqueued work has read them (the caller synchronises per view)
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().mi355gs_tracker_run(ctypes.c_void_p(self.handle), _lib.stream_ptr(dev), int(sh_degree), _lib.ptr(gt),
-                                                      _lib.ptr(proj), tx, ty, _lib.ptr(bg), _lib.ptr(sched), int(num_iter), int(first_iter),
-                                                      int(n_iters), _lib.ptr(state), _lib.ptr(pt), _lib.ptr(lt), _lib.ptr(gt_)),
-                       "tracker_run")
+        _lib.call(dev, "tracker_run", self._h, _lib.STREAM, int(sh_degree), gt, proj, tx, ty, bg, sched, int(num_iter), int(first_iter),
+                  int(n_iters), state, pt, lt, gt_)
 
 
 def _state_word(st: torch.Tensor, i: int) -> int:
@@ -205,7 +164,7 @@ def optimize_view_pose_fused(view, gaussians, pipe, background, init_pose: torch
     W, H, D = int(view.image_width), int(view.image_height), int(gaussians.active_sh_degree)
     if capacity is None:
         probe = FusedPoseTracker(gaussians, W, H, 1)
-        capacity = int(BinningPolicy.slack * probe.count(view, D, pose0)) + BinningPolicy.pad
+        capacity = BinningPolicy.capacity_for(probe.count(view, D, pose0))
         probe.close()
     reruns = 0
     while True:
@@ -220,7 +179,7 @@ def optimize_view_pose_fused(view, gaussians, pipe, background, init_pose: torch
         if _state_word(st, S_FLAG) == 0:
             break
         reruns += 1
-        capacity = max(int(BinningPolicy.slack * _state_word(st, S_COUNT)) + BinningPolicy.pad, 2 * capacity)
+        capacity = BinningPolicy.regrown(_state_word(st, S_COUNT), capacity)
     pose = st[S_CAND:S_CAND + 7].to(dev)
     with torch.no_grad():
         final = render(view, gaussians, pipe, background, camera_pose=pose)["render"]

@@ -10,7 +10,6 @@ the reference's run_infer.sh after `train.training()`.
 from __future__ import annotations
 
 import copy
-import ctypes
 import math
 import os
 from typing import List, Optional
@@ -22,6 +21,7 @@ from . import _lib
 from .camera_path import save_interpolate_pose
 from .diff_gaussian_rasterization import BinningPolicy
 from .gaussian_renderer import render
+from .handles import FrozenSceneHandle
 from .pose_utils import get_tensor_from_camera
 from .scene_io import load_cameras
 
@@ -38,44 +38,13 @@ def quantize_rgb8(image: torch.Tensor, out: torch.Tensor | None = None) -> torch
         out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous():
         raise ValueError(f"quantize_rgb8 writes a contiguous uint8 [{H},{W},3] tensor")
-    with _lib.on_device(dev):
-        _lib.check(_lib.lib().mi355gs_rgb8_from_planar(_lib.stream_ptr(dev), H, W, _lib.ptr(image), _lib.ptr(out)), "rgb8_from_planar")
+    _lib.call(dev, "rgb8_from_planar", _lib.STREAM, H, W, image, out)
     return out
 
 
-class FusedPathRenderer:
+class FusedPathRenderer(FrozenSceneHandle):
     """Handle of mi355gs_path_*: the frozen Gaussians' raw parameters, one image size and an instance capacity."""
-
-    def __init__(self, gaussians, W: int, H: int, capacity: int):
-        g = gaussians
-        self.params = [t.detach() for t in (g._xyz, g._features_dc, g._features_rest, g._opacity, g._scaling, g._rotation)]
-        dev = _lib.require_device(*self.params)
-        P = int(self.params[0].shape[0])
-        M = 1 + int(self.params[2].shape[1]) if self.params[2].dim() == 3 else 1
-        shapes = ((P, 3), (P, 1, 3), (P, M - 1, 3), (P, 1), (P, 3), (P, 4))
-        for t, shape in zip(self.params, shapes):   # the library indexes raw pointers with these shapes
-            if t.dtype != torch.float32 or tuple(t.shape) != shape:
-                raise ValueError(f"path rendering needs float32 parameters of shape {shape}, got {tuple(t.shape)} {t.dtype}")
-        L = _lib.lib()
-        self.dev, self.P, self.M, self.W, self.H, self.capacity = dev, P, M, int(W), int(H), int(capacity)
-        nbytes = L.mi355gs_path_workspace_bytes(P, self.W, self.H, self.capacity)
-        if not nbytes:
-            raise ValueError("mi355gs_path_workspace_bytes rejected the sizes")
-        self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        self.handle = L.mi355gs_path_create(P, M, self.W, self.H, self.capacity, *[_lib.ptr(t) for t in self.params],
-                                            _lib.ptr(self.workspace))
-        if not self.handle:
-            raise RuntimeError("mi355gs_path_create failed")
-
-    def close(self):
-        handle, self.handle = getattr(self, "handle", None), None
-        if handle:
-            try:
-                _lib.lib().mi355gs_path_destroy(ctypes.c_void_p(handle))
-            except Exception:  # interpreter shutdown
-                pass
-
-    __del__ = close
+    prefix, phrase = "path", "path rendering"
 
     def render(self, proj: torch.Tensor, tanfovx: float, tanfovy: float, background: torch.Tensor, sh_degree: int, poses: torch.Tensor,
                frames: torch.Tensor, counts: torch.Tensor, first: int = 0, n: int | None = None):
@@ -99,10 +68,8 @@ class FusedPathRenderer:
         if proj.numel() != 16 or bg.numel() != 3:
             raise ValueError("the projection matrix needs 16 floats and the background 3")
         self._keep = (proj, bg, poses)   # alive until the enqueued work has read them (the caller synchronises per group)
-        with _lib.on_device(dev):
-            _lib.check(_lib.lib().mi355gs_path_render(ctypes.c_void_p(self.handle), _lib.stream_ptr(dev), int(sh_degree), _lib.ptr(proj),
-                                                      float(tanfovx), float(tanfovy), _lib.ptr(bg), _lib.ptr(poses), int(first), int(n),
-                                                      _lib.ptr(frames), _lib.ptr(counts)), "path_render")
+        _lib.call(dev, "path_render", self._h, _lib.STREAM, int(sh_degree), proj, float(tanfovx), float(tanfovy), bg, poses, int(first), int(n),
+                  frames, counts)
 
 
 def _stacked_on_host(tensors) -> torch.Tensor:
@@ -174,7 +141,7 @@ def render_pose_path(views: List, gaussians, pipe, background, poses: torch.Tens
         if cap is None:   # the exact count of the first pose: one frame through a handle of the smallest size
             probe = FusedPathRenderer(gaussians, W, H, 1)
             probe.render(proj, tx, ty, background, D, gposes, frames, counts, 0, 1)
-            cap = int(BinningPolicy.slack * int(counts[0])) + BinningPolicy.pad
+            cap = BinningPolicy.capacity_for(int(counts[0]))
             probe.close()
         todo = None   # frames to render: all of them first, then those whose count exceeded the capacity
         while True:
@@ -190,7 +157,7 @@ def render_pose_path(views: List, gaussians, pipe, background, poses: torch.Tens
             if not todo:
                 break
             reruns += len(todo)
-            cap = max(int(BinningPolicy.slack * int(host_counts.max())) + BinningPolicy.pad, 2 * cap)
+            cap = BinningPolicy.regrown(int(host_counts.max()), cap)
         out_frames.append(frames)
         out_counts.append(host_counts)
     same = all(f.shape[1:] == out_frames[0].shape[1:] for f in out_frames)

@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _frames, _lib
 
 PRECISION_BITS = 22          # libImaging Resample.c: 32 - 8 - 2
 MAX_SIZE = 65535             # include/mi355gs.h: N and every size of one mi355gs_resample_rgb8 call
@@ -127,13 +127,8 @@ def resize_rgb8(images: torch.Tensor, size, resample="bicubic", window=None, out
     An axis whose size does not change is not resampled, as in PIL.
     Raises ValueError for anything but a contiguous uint8 device tensor of that shape, an empty target, a window outside it, or
     sizes beyond the library's limits."""
-    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() not in (3, 4) or images.shape[-1] != 3:
-        raise ValueError("resize_rgb8 takes a uint8 [N,H,W,3] or [H,W,3] tensor, got "
-                         f"{tuple(images.shape) if isinstance(images, torch.Tensor) else type(images)} {getattr(images, 'dtype', '')}")
-    if not images.is_cuda and not _lib._TEST_MODE:
-        raise ValueError("resize_rgb8 resizes on the GPU only (got a CPU tensor; there is no CPU fallback): pass images.to(device)")
-    if not images.is_contiguous():
-        raise ValueError("resize_rgb8 takes a contiguous tensor")
+    single = isinstance(images, torch.Tensor) and images.dim() == 3
+    images, N, H, W = _frames.check_frames("resize_rgb8", images, verb="resizes", arg="images")
     name = filter_name(resample)
     names = (out,) if isinstance(out, str) else tuple(out)
     if not names or any(not isinstance(o, str) or o not in OUTPUTS for o in names) or len(set(names)) != len(names):
@@ -144,12 +139,6 @@ def resize_rgb8(images: torch.Tensor, size, resample="bicubic", window=None, out
         raise ValueError(f"size must be (width, height), got {size!r}") from None
     if Wo <= 0 or Ho <= 0:
         raise ValueError(f"empty target: {Wo} x {Ho}")
-    single = images.dim() == 3
-    if single:
-        images = images[None]
-    N, H, W = (int(s) for s in images.shape[:3])
-    if H <= 0 or W <= 0:
-        raise ValueError(f"empty images: {H} x {W}")
     if window is None:
         x0, y0, w, h = 0, 0, Wo, Ho
     else:
@@ -165,7 +154,6 @@ def resize_rgb8(images: torch.Tensor, size, resample="bicubic", window=None, out
     results = {o: torch.empty((N, h, w, 3) if o == "rgb8" else (N, 3, h, w), dtype=torch.uint8 if o == "rgb8" else torch.float32, device=dev)
                for o in names}
     if N:
-        L = _lib.lib()
         kx = bx = ky = by = scratch = None
         ksx = ksy = row0 = rows = 0
         if Wo != W:
@@ -177,15 +165,10 @@ def resize_rgb8(images: torch.Tensor, size, resample="bicubic", window=None, out
             if kx is not None:   # the source rows the window's vertical taps reach
                 row0 = int(host[y0:y0 + h, 0].min())
                 rows = int((host[y0:y0 + h, 0] + host[y0:y0 + h, 1]).max()) - row0
-                nbytes = int(L.mi355gs_resample_rgb8_scratch_bytes(N, rows, w))
-                if not nbytes:
-                    raise ValueError(f"mi355gs_resample_rgb8 does not take an intermediate of {N} x {rows} x {w} (include/mi355gs.h: the limits)")
-                scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            _lib.check(L.mi355gs_resample_rgb8(_lib.stream_ptr(dev), N, H, W, Ho, Wo, images.data_ptr(), _lib.ptr(kx), _lib.ptr(bx), ksx,
-                                               _lib.ptr(ky), _lib.ptr(by), ksy, x0, y0, w, h, row0, rows, _lib.ptr(scratch),
-                                               _lib.ptr(results.get("rgb8")), _lib.ptr(results.get("unit")),
-                                               _lib.ptr(results.get("normalized"))), "resample_rgb8")
+                scratch = _lib.scratch(dev, "resample_rgb8_scratch_bytes", N, rows, w, what=f"mi355gs_resample_rgb8 does not take an "
+                                       f"intermediate of {N} x {rows} x {w} (include/mi355gs.h: the limits)")
+        _lib.call(dev, "resample_rgb8", _lib.STREAM, N, H, W, Ho, Wo, images, kx, bx, ksx, ky, by, ksy, x0, y0, w, h, row0, rows, scratch,
+                  results.get("rgb8"), results.get("unit"), results.get("normalized"))
     got = tuple(results[o][0] if single else results[o] for o in names)
     return got[0] if isinstance(out, str) else got
 

@@ -12,8 +12,5 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     dev = _lib.require_device(pts)
     n = pts.shape[0]
     out = torch.zeros(n, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    scratch = torch.empty(max(int(L.mi355gs_knn_scratch_bytes(n)), 1), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(L.mi355gs_knn_dist2(_lib.stream_ptr(dev), n, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(scratch)), "knn_dist2")
+    _lib.call(dev, "knn_dist2", _lib.STREAM, n, pts, out, _lib.scratch(dev, "knn_scratch_bytes", n, what=None))
     return out

@@ -23,6 +23,7 @@ from .optim import PerPointAdam
 from .fused_ssim import fused_l1_ssim_loss, fused_ssim
 from .diff_gaussian_rasterization import BinningPolicy, binning_hint
 from .gaussian_renderer import render
+from .handles import LibraryHandle
 from .pose_utils import quadmultiply
 from .scene import GaussianModel, confidence_to_lr_modifiers
 from .synthetic import PointmapScene
@@ -298,7 +299,7 @@ def _fused_synced_iteration(st: TrainState):
                 with binning_hint(hint_key(st, cam)):
                     render(cam, st.gaussians, st.pipe, st.background, camera_pose=st.gaussians.get_RT(cam.uid))
         need = max(BinningPolicy.known[hint_key(st, c)] for c in st.cameras)
-        tr = st._trainer = FusedTrainer(st, int(BinningPolicy.slack * need) + BinningPolicy.pad)
+        tr = st._trainer = FusedTrainer(st, BinningPolicy.capacity_for(need))
         # loss and instance count are stored by the kernels that produce them straight into words of pinned, device-mapped
         # host memory (count as int32: a float32 detour would round counts above 2^24, reachable at 1 M Gaussians / 1080p, and
         # could hide an overflow of a few instances): the iteration's read-back is a poll of these words, not a copy.  Two pairs:
@@ -361,11 +362,12 @@ def train_iteration(st: TrainState, fused_loss: bool = True, sync_loss: bool = T
     return out
 
 
-class FusedTrainer:
+class FusedTrainer(LibraryHandle):
     """Whole iteration in one library call (mi355gs_trainer_step): same kernels as the op-by-op path, no autograd
     graph, no temporaries, 11 launches.  Used by RunAhead whenever the configuration is the one the reference's
     scripts run (SH colours of any active degree, scale/rotation covariance, PerPointAdam with pose optimisation)."""
 
+    prefix = "trainer"
     ORDER = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation", "P")
 
     @staticmethod
@@ -396,7 +398,6 @@ class FusedTrainer:
     def __init__(self, st: TrainState, capacity: int):
         self.st, self.capacity = st, int(capacity)
         g = st.gaussians
-        L = _lib.lib()
         self.params = [getattr(g, n) for n in self.ORDER]
         dev = _lib.require_device(*[p.data for p in self.params])
         self.dev = dev
@@ -407,17 +408,14 @@ class FusedTrainer:
         P, V = g._xyz.shape[0], g.P.shape[0]
         cam = st.cameras[0]
         self.W, self.H = int(cam.image_width), int(cam.image_height)
-        nbytes = L.mi355gs_trainer_workspace_bytes(P, self.W, self.H, V, self.capacity)
-        self.workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         PTR = ctypes.c_void_p * 7
         m = PTR(*[g.optimizer.state[p]["exp_avg"].data_ptr() for p in self.params])
         v = PTR(*[g.optimizer.state[p]["exp_avg_sq"].data_ptr() for p in self.params])
         pplr = g.optimizer.param_groups[0].get("per_point_lr")
         self._keep = (m, v, pplr)
-        self.handle = L.mi355gs_trainer_create(P, self.W, self.H, V, self.capacity, *[_lib.ptr(p.data) for p in self.params], m, v,
-                                               _lib.ptr(pplr), _lib.ptr(self.workspace))
-        if not self.handle:
-            raise RuntimeError("mi355gs_trainer_create failed")
+        sizes = (P, self.W, self.H, V, self.capacity)
+        self._open(dev, sizes, lambda ws: (*sizes, *[p.data for p in self.params], m, v, pplr, ws),
+                   refused=RuntimeError("mi355gs_trainer_workspace_bytes rejected the sizes"))
         self.num_rendered = torch.zeros(1, dtype=torch.int32, device=dev)
         # Asynchronous verification: the step's instance count is stored by the tile-scan kernel STRAIGHT into a slot of this
         # ring of pinned host memory (device-mapped), so no device-to-host copy — a 4-5 us blit kernel on the training stream,
@@ -425,26 +423,16 @@ class FusedTrainer:
         self._count_ring = torch.zeros(self.COUNT_RING, dtype=torch.int32, pin_memory=(dev.type == "cuda"))
         self._count_next = 0
 
-    def close(self):
-        handle, self.handle = getattr(self, "handle", None), None
-        if handle:
-            try:
-                _lib.lib().mi355gs_trainer_destroy(ctypes.c_void_p(handle))
-            except Exception:  # interpreter shutdown: module globals may already be gone (the handle is host memory only)
-                pass
-
     def gradients(self) -> dict:
         """Copies of the gradients the last `step` left in the workspace, keyed like the GaussianModel attributes
         (what `.grad` holds on the autograd path) — for tests and diagnostics."""
         L, base, out = _lib.lib(), self.workspace.data_ptr(), {}
         for k, (name, p) in enumerate(zip(self.ORDER, self.params)):
-            addr = L.mi355gs_trainer_grad(ctypes.c_void_p(self.handle), k)
+            addr = L.mi355gs_trainer_grad(self._h, k)
             off, nbytes = int(addr) - base, 4 * p.numel()
             assert addr and 0 <= off and off + nbytes <= self.workspace.numel(), (name, off)
             out[name] = self.workspace[off:off + nbytes].view(torch.float32).view(p.shape).clone()
         return out
-
-    __del__ = close
 
     COUNT_RING = 256
 
@@ -570,7 +558,7 @@ class RunAhead:
         need = max(BinningPolicy.known[hint_key(st, c)] for c in st.cameras)
         if self.trainer is not None:
             self.trainer.close()
-        self.trainer = FusedTrainer(st, int(BinningPolicy.slack * need) + BinningPolicy.pad)
+        self.trainer = FusedTrainer(st, BinningPolicy.capacity_for(need))
 
     def _tensors(self):
         g = self.st.gaussians

@@ -83,7 +83,7 @@ def run_tracker(g, view, bg, degree, pose0, num_iter, det=False):
         probe = FusedPoseTracker(g, W, H, 1)
         cnt = probe.count(view, degree, pose0)
         probe.close()
-        tr = FusedPoseTracker(g, W, H, int(BinningPolicy.slack * cnt) + BinningPolicy.pad)
+        tr = FusedPoseTracker(g, W, H, BinningPolicy.capacity_for(cnt))
         state = FusedPoseTracker.initial_state(pose0)
         traces = (torch.empty(num_iter, 7, device=dev), torch.empty(num_iter, device=dev), torch.empty(num_iter, 7, device=dev))
         tr.run(view, bg, degree, state, num_iter, traces=traces)
