@@ -545,6 +545,55 @@ int mi355gs_lpips_vgg_rgb8(void* stream, int N, int H, int W, const uint8_t* a, 
                            const float* weights, void* scratch, float* lpips, float* taps);
 
 /* ----------------------------------------------------------------------------------------------
+ * MASt3R's transformer trunk (csrc/vit.hip; reference dust3r/model.py:127-190 for the wiring, the published croco blocks for
+ * the arithmetic): a ViT encoder over 16 x 16 patches, decoder_embed, and two decoders whose blocks cross-attend to each other's
+ * previous-layer output.  float32 throughout; every linear layer is a k-ordered fused-multiply-add chain
+ * (v_mfma_f32_32x32x2_f32), started at 0, the bias added last.  No atomics: equal bits run to run, and a token's result does not
+ * depend on how many images or edges share the call.
+ *   block(x):        x += proj(attention(qkv(norm1(x))));  x += fc2(gelu(fc1(norm2(x))))            (GELU: exact erf)
+ *   dec_block(x, y): x += proj(attention(qkv(norm1(x))));  x += cproj(attention(projq(norm2(x)), projk(norm_y(y)), projv(norm_y(y))));
+ *                    x += fc2(gelu(fc1(norm3(x))))
+ *   LayerNorm: eps 1e-6, biased variance.  attention: heads of 64 channels, q and k turned by RoPE2D (the first 32 channels of a
+ *   head by the token's grid row, the last 32 by its column; channel j of a half pairs with j +- 16), softmax(q k^T / 8) v.
+ *   Token n of an image sits at row n / Wt, column n % Wt of the Ht x Wt grid.
+ * cfg: the sizes.  hooks: hooks[0] = 0 < hooks[1] < hooks[2] < hooks[3] = dec_depth — the decoder layers whose outputs a head reads.
+ * weights: ONE device blob of floats, 16-byte aligned; a linear layer [K -> N] is the matrix [K][N] (torch's weight transposed)
+ *   followed by its bias [N], a LayerNorm its weight [D] then its bias [D].  In order:
+ *     patch embedding [768 -> enc_dim] (row (c 16 + py) 16 + px: torch's convolution weight flattened, transposed);
+ *     enc_depth blocks of: norm1, qkv [D -> 3D] (column which D + head 64 + d), proj [D -> D], norm2, fc1 [D -> 4D], fc2 [4D -> D];
+ *     enc_norm; decoder_embed [enc_dim -> dec_dim];
+ *     dec_depth blocks of side 1, then dec_depth blocks of side 2, each: norm1, qkv, proj, norm_y, norm2, projq, projk, projv,
+ *     cross proj (four [D -> D]), norm3, fc1, fc2;  dec_norm.
+ * rope: device floats, cos [P][16] then sin [P][16], P = max(Ht, Wt): cos / sin of p base^(-2 i / 32), i = 0..15 (the caller
+ *   builds it once per grid; MASt3R's base is 100).
+ * mi355gs_vit_encode: images float32 planar [V][3][16 Ht][16 Wt] -> feat [V][Ht Wt][enc_dim] (after enc_norm).
+ * mi355gs_vit_decode: feat as above and E directed edges (i, j), int32 [E][2] in HOST memory: checked against V, then copied
+ *   into the scratch with hipMemcpyAsync on the stream.  From pageable memory the runtime has taken the bytes when the call
+ *   returns (the caller may free them then), and MAY make the host wait for the stream's earlier work to do so — the one place
+ *   where a call can block; pinned memory is copied when the stream reaches the copy and must stay valid until then.
+ *   -> per side four tensors: out1[0] = feat of image i per edge, [E][Ht Wt][enc_dim]; out1[1..2] = side
+ *   1 after decoder layers hooks[1], hooks[2]; out1[3] = dec_norm of side 1 after the last layer, [E][Ht Wt][dec_dim] each; out2
+ *   likewise for image j and side 2.  Side 1 of layer l reads (side 1, side 2) of layer l - 1, side 2 reads (side 2, side 1).
+ * scratch: the query's bytes of device memory, 16-byte aligned, owned by the caller (0 = the sizes are refused).  Launches on the
+ * caller's stream; no allocation, no memset, and no host synchronisation of the library's own (decode's edge copy: above).
+ * Limits (MI355GS_EINVAL beyond them, as for null pointers and weights, images, feat, scratch or outputs off a 16-byte boundary):
+ * enc_dim, dec_dim multiples of 64 in [64, 1024]; heads x 64 = width; depths in [1, 256]; patch = 16; Ht Wt <= 4096; V <= 256;
+ * E <= 65535; every edge index in [0, V).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mi355gs_vit_config {
+  int enc_dim, enc_depth, enc_heads;
+  int dec_dim, dec_depth, dec_heads;
+  int patch;
+  int hooks[4];
+} mi355gs_vit_config;
+size_t mi355gs_vit_encode_scratch_bytes(const mi355gs_vit_config* cfg, int Ht, int Wt, int V);
+int mi355gs_vit_encode(void* stream, const mi355gs_vit_config* cfg, const float* weights, const float* rope, int Ht, int Wt, int V,
+                       const float* images, void* scratch, float* feat);
+size_t mi355gs_vit_decode_scratch_bytes(const mi355gs_vit_config* cfg, int Ht, int Wt, int E);
+int mi355gs_vit_decode(void* stream, const mi355gs_vit_config* cfg, const float* weights, const float* rope, int Ht, int Wt, int V, int E,
+                       const int32_t* edges, const float* feat, void* scratch, float* const out1[4], float* const out2[4]);
+
+/* ----------------------------------------------------------------------------------------------
  * PNG files of 8-bit RGB frames, encoded on the device (csrc/png.hip).  frames: uint8 [N][H][W][3] in device memory, any base
  * address (a slice of a stack is fine).  out receives the N files back to back: file i is out[offsets[i] : offsets[i+1]], offsets
  * a device array of N + 1.  Every file is: signature, IHDR (8-bit RGB, no interlace), one IDAT per block of rows_per_block

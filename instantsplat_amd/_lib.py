@@ -95,6 +95,10 @@ _SIGNATURES = {
     "mi355gs_jpeg_rgb8": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "mi355gs_lpips_vgg_scratch_bytes": (c_size_t, [c_int, c_int, c_int, _P]),
     "mi355gs_lpips_vgg_rgb8": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "mi355gs_vit_encode_scratch_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "mi355gs_vit_encode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "mi355gs_vit_decode_scratch_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "mi355gs_vit_decode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "mi355gs_pointmap_stats_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mi355gs_pointmap_stats": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "mi355gs_covis_masks": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, _P]),

@@ -27,39 +27,7 @@ constexpr int LP_TAP_PIX = 256;      // pixels of a tap workgroup: 4 waves x 64
 constexpr int LP_MAX_C = 512;
 constexpr float LP_EPS = 1e-10f;
 
-#ifdef __clang__
-typedef float lp_acc16 __attribute__((ext_vector_type(16)));
-#else
-struct lp_acc16 {
-  float v[16];
-  float& operator[](int i) { return v[i]; }
-  float operator[](int i) const { return v[i]; }
-};
-#endif
-// 16 bytes moved at once.  (Arrays of HIP's float4 class held across the K loop are not promoted to registers by hipcc.)
-#ifdef __clang__
-typedef float lp_f4 __attribute__((ext_vector_type(4)));
-#else
-typedef float4 lp_f4;
-#endif
-
-// The one place the matrix instruction is named.  C (32x32, float32) += A (32x2) B (2x32) on one wave, the operands read from
-// LDS: A[m][k] = As[m * lda + k], B[k][n] = Bs[k * ldb + n].  Lane l supplies A[l & 31][l >> 5] and B[l >> 5][l & 31] and holds
-// C[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31] in register r.  The instruction rounds like the chain below (one rounding per
-// product-and-add, k ascending), so the portable body — the host pass and the g++ build of the CPU test tier, where every lane
-// reads its operands from the same LDS image — computes the same bits.
-__device__ __forceinline__ void lp_mfma_32x32x2(lp_acc16& c, const float* As, int lda, const float* Bs, int ldb, int lane) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  c = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(lane & 31) * lda + (lane >> 5)], Bs[(lane >> 5) * ldb + (lane & 31)], c, 0, 0, 0);
-#else
-  for (int k = 0; k < 2; ++k) {
-    const float b = Bs[k * ldb + (lane & 31)];
-    for (int r = 0; r < 16; ++r) c[r] = fmaf(As[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * lda + k], b, c[r]);
-  }
-#endif
-}
-
-__device__ __forceinline__ int lp_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+// lp_acc16, lp_f4, lp_mfma_32x32x2 and lp_acc_row: common.h (shared with vit.hip)
 
 // ---------------------------------------------------------------------------------------------------- first layer
 // (byte / 255 - mean) / std as the reference's float32 tensor ops round it; the zero padding pads the NORMALISED image.
