@@ -594,6 +594,65 @@ int mi355gs_vit_decode(void* stream, const mi355gs_vit_config* cfg, const float*
                        const int32_t* edges, const float* feat, void* scratch, float* const out1[4], float* const out2[4]);
 
 /* ----------------------------------------------------------------------------------------------
+ * MASt3R's dense heads (csrc/dpt.hip): what turns mi355gs_vit_decode's four hooked tensors of one side into that side's output.
+ * The order of operations is dust3r/heads/dpt_head.py's and mast3r/catmlp_dpt_head.py's; the block definitions (croco's DPT
+ * adapter, its ResidualConvUnit and FeatureFusionBlock, its Mlp) are the published ones, recalled.  float32 throughout,
+ * activations channels-last; every product is a k-ordered fused-multiply-add chain (v_mfma_f32_32x32x2_f32) started at 0, the bias
+ * added last, a residual after the bias.  No atomics: equal bits run to run, and a pixel's result does not depend on how many
+ * edges share the call.
+ *
+ * mi355gs_dpt_head, on a grid of Ht x Wt tokens (H = 16 Ht, W = 16 Wt; token n at row n / Wt, column n % Wt):
+ *   act_postprocess[k] on hooks[k] [E][Ht Wt][dim_tokens[k]]:
+ *     k = 0: 1x1 -> layer_dims[0], ConvTranspose kernel 4 stride 4 (4 Ht x 4 Wt);  k = 1: 1x1 -> layer_dims[1], ConvTranspose kernel 2
+ *     stride 2;  k = 2: 1x1 -> layer_dims[2];  k = 3: 1x1 -> layer_dims[3], 3x3 stride 2 padding 1 (ceil(Ht / 2) x ceil(Wt / 2))
+ *   L[k] = layer_rn[k]: 3x3, padding 1, layer_dims[k] -> F = feature_dim, no bias
+ *   rcu(x) = x + conv2(relu(conv1(relu(x))))  (3x3, F -> F, bias; the skip adds the un-rectified x)
+ *   fusion(a[, b]) = out_conv(up2(rcu2(a [+ rcu1(b)])))  (up2: bilinear x 2, align_corners; out_conv 1x1 F -> F)
+ *   path_4 = fusion4(L[3]) cropped to L[2]'s size; path_3 = fusion3(path_4, L[2]); path_2 = fusion2(path_3, L[1]);
+ *   path_1 = fusion1(path_2, L[0])  (8 Ht x 8 Wt)
+ *   head: 3x3 F -> F / 2, up2 (H x W), 3x3 F / 2 -> last_dim, ReLU, 1x1 last_dim -> 4 = (x, y, z, c)
+ *   postprocess: d = |xyz|, pts3d = xyz / max(d, 1e-8) * expm1(d);  conf = conf_vmin + min(exp(c), conf_vmax - conf_vmin)
+ *   -> pts3d [E][H][W][3], conf [E][H][W]; raw4 (may be NULL; 16-byte aligned) [E][H][W][4] = (x, y, z, c).
+ *   The last_dim-channel tensor never reaches memory: ReLU, the 1x1 and postprocess run in the last convolution's epilogue.
+ * weights of a head: ONE device blob of floats, 16-byte aligned.  A 1x1 convolution or linear layer [K -> N] is the matrix [K][N]
+ * followed by its bias [N]; a 3x3 convolution [9 Cin][Cout], row (3 ky + kx) Cin + ci (torch's weight.permute(2, 3, 1, 0)), followed
+ * by its bias where it has one; a ConvTranspose of stride s [C][s s C], column (dy s + dx) C + co (torch's weight.permute(0, 2, 3, 1)),
+ * followed by its bias repeated s s times.  In order:
+ *   act_postprocess: 0.0, 0.1 (transpose), 1.0, 1.1 (transpose), 2.0, 3.0, 3.1 (3x3);  layer_rn 0..3 (no bias);
+ *   refinenet4: resConfUnit2.conv1, .conv2, out_conv;  refinenet3, 2, 1 each: resConfUnit1.conv1, .conv2, resConfUnit2.conv1, .conv2,
+ *   out_conv;  head.0, head.2, head.4 as [last_dim][32] (columns 4.. zero) with its bias padded to [32].
+ * mi355gs_dpt_head_tap_offset: the byte offset inside the scratch at which the call leaves intermediate `which`, channels-last with
+ *   F channels: 0..3 = L[0..3], 4..7 = path_4, path_3, path_2, path_1 (0 = refused; no buffer starts at offset 0).
+ *
+ * mi355gs_local_features: fc2(gelu(fc1(cat(hook0, hook3)))) per token, [dim_tokens[0] + dim_tokens[3] -> mlp_hidden ->
+ *   (local_feat_dim + two_confs) 256], pixel_shuffle(16), desc [E][H][W][local_feat_dim] = the first local_feat_dim channels over
+ *   their norm, desc_conf [E][H][W] = desc_conf_vmin + min(exp(last channel), desc_conf_vmax - desc_conf_vmin) when two_confs
+ *   (else desc_conf is not written and may be NULL).  weights: fc1 [K][hidden] + bias, fc2 [hidden][out] + bias.
+ *
+ * scratch: the query's bytes of device memory, 16-byte aligned, owned by the caller (0 = the sizes are refused).  Launches on
+ * the caller's stream; no allocation, no memset, no host synchronisation.
+ * Limits (MI355GS_EINVAL beyond them, as for null pointers and weights, hooks, scratch or raw4 off a 16-byte boundary):
+ * dim_tokens multiples of 32 in [32, 4096]; layer_dims multiples of 32 in [32, 1024]; feature_dim a multiple of 64 in [64, 256]
+ * (F / 2 <= 128); last_dim a multiple of 32 in [32, 128]; mlp_hidden a multiple of 32 in [32, 32768]; local_feat_dim in [1, 255];
+ * vmax > vmin; Ht Wt <= 4096; E <= 65535; 4 E H W <= 2^31 - 1 (callers split E).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mi355gs_dpt_config {
+  int dim_tokens[4];
+  int layer_dims[4];
+  int feature_dim, last_dim;
+  int mlp_hidden, local_feat_dim, two_confs;
+  float conf_vmin, conf_vmax;
+  float desc_conf_vmin, desc_conf_vmax;
+} mi355gs_dpt_config;
+size_t mi355gs_dpt_head_scratch_bytes(const mi355gs_dpt_config* cfg, int Ht, int Wt, int E);
+size_t mi355gs_dpt_head_tap_offset(const mi355gs_dpt_config* cfg, int Ht, int Wt, int E, int which);
+int mi355gs_dpt_head(void* stream, const mi355gs_dpt_config* cfg, const float* weights, int Ht, int Wt, int E, const float* const hooks[4],
+                     void* scratch, float* pts3d, float* conf, float* raw4);
+size_t mi355gs_local_features_scratch_bytes(const mi355gs_dpt_config* cfg, int Ht, int Wt, int E);
+int mi355gs_local_features(void* stream, const mi355gs_dpt_config* cfg, const float* weights, int Ht, int Wt, int E, const float* hook0,
+                           const float* hook3, void* scratch, float* desc, float* desc_conf);
+
+/* ----------------------------------------------------------------------------------------------
  * PNG files of 8-bit RGB frames, encoded on the device (csrc/png.hip).  frames: uint8 [N][H][W][3] in device memory, any base
  * address (a slice of a stack is fine).  out receives the N files back to back: file i is out[offsets[i] : offsets[i+1]], offsets
  * a device array of N + 1.  Every file is: signature, IHDR (8-bit RGB, no interlace), one IDAT per block of rows_per_block

@@ -99,6 +99,11 @@ _SIGNATURES = {
     "mi355gs_vit_encode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "mi355gs_vit_decode_scratch_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
     "mi355gs_vit_decode": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "mi355gs_dpt_head_scratch_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "mi355gs_dpt_head_tap_offset": (c_size_t, [_P, c_int, c_int, c_int, c_int]),
+    "mi355gs_dpt_head": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "mi355gs_local_features_scratch_bytes": (c_size_t, [_P, c_int, c_int, c_int]),
+    "mi355gs_local_features": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "mi355gs_pointmap_stats_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mi355gs_pointmap_stats": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "mi355gs_covis_masks": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_float, _P]),

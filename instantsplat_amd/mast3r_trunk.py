@@ -5,8 +5,8 @@ decoded, where the reference's loop encodes both images of every pair (2 V (V - 
 
 The arithmetic is built and checked here against a float64 restatement on seeded weights (tests/vit_util.py); the block
 definitions are the published croco ones, recalled — the trained checkpoint is not part of this package and no test pins a real
-output.  The DPT heads, the local-feature MLP and the assembly of `inference()`'s output are NOT here yet: `decode` returns what the
-heads read.
+output.  The DPT heads, the local-feature MLP and the assembly of `inference()`'s output are mast3r_heads.py and mast3r.py: `decode`
+returns what the heads read.
 """
 from __future__ import annotations
 
