@@ -289,8 +289,8 @@ __device__ __forceinline__ uint32_t gs_physical_cu() {
   return ((xcc & 7u) << 6) | (((hw >> 13) & 3u) << 4) | ((hw >> 8) & 15u);
 }
 
-// ---- The f32-input matrix instruction (lpips.hip, vit.hip): the accumulator type, 16 bytes moved at once, and the one helper
-// that names the instruction.
+// ---- The f32-input matrix instruction (mm_tile.h: lpips.hip, vit.hip, dpt.hip): the accumulator type, 16 bytes moved at once,
+// and the one helper that names the instruction.
 #ifdef __clang__
 typedef float lp_acc16 __attribute__((ext_vector_type(16)));
 #else
@@ -301,10 +301,15 @@ struct lp_acc16 {
 };
 #endif
 // 16 bytes moved at once.  (Arrays of HIP's float4 class held across the K loop are not promoted to registers by hipcc.)
+// LP_AT / LP_ATC: element k of one (hipcc: the vector type's own subscript, which stays in registers; g++: the struct's storage).
 #ifdef __clang__
 typedef float lp_f4 __attribute__((ext_vector_type(4)));
+#define LP_AT(v, k) ((v)[k])
+#define LP_ATC(v, k) ((v)[k])
 #else
 typedef float4 lp_f4;
+#define LP_AT(v, k) (((float*)&(v))[k])
+#define LP_ATC(v, k) (((const float*)&(v))[k])
 #endif
 
 // The one place the matrix instruction is named.  C (32x32, float32) += A (32x2) B (2x32) on one wave, the operands read from

@@ -3,11 +3,11 @@
 // (dust3r/heads/dpt_head.py for the order of operations, dust3r/heads/postprocess.py for the last step), and the local-feature
 // MLP of mast3r/catmlp_dpt_head.py.  float32 throughout, activations channels-last [edge][y][x][channel].
 //
-//   k_vit_gemm     (vit_gemm.h) every 1 x 1 convolution, both ConvTransposes (a GEMM to [row][s s C]) and the MLP
+//   k_vit_gemm     (mm_tile.h) every 1 x 1 convolution, both ConvTransposes (a GEMM to [row][s s C]) and the MLP
 //   k_dpt_scatter  the ConvTranspose's store: [token][(dy s + dx) C + c] -> pixel (s y + dy, s x + dx), one float4 per thread
-//   k_dpt_conv     3 x 3 implicit GEMM as k_lpips_conv: 128 output pixels x (32, 64 or 128) outputs per workgroup, K in chunks of 32
-//                  channels of one tap, register prefetch under the matrix instructions, predicated border loads.  Switches: ReLU on
-//                  the staged input, bias or none, stride 1 or 2, up to two residual tensors added in the epilogue.
+//   k_dpt_conv     3 x 3 implicit GEMM on the shared K loop and tap fetch (mm_tile.h), as k_lpips_conv: 128 output pixels x (32, 64
+//                  or 128) outputs per workgroup.  Switches: ReLU on the staged input, bias or none, stride 1 or 2, up to two
+//                  residual tensors added in the epilogue.
 //   k_dpt_up2      bilinear x 2, align_corners = True, one float4 of channels per thread; its output size may be smaller than
 //                  twice the input (refinenet4's crop: the steps behind it are per pixel, so the crop is taken here)
 //   k_dpt_final    head.2 (3 x 3, F / 2 -> last_dim) with every output channel of its 128 pixels in one workgroup; the epilogue
@@ -17,126 +17,28 @@
 // No atomics, no memset, no allocation, no host synchronisation; equal bits run to run, and a pixel's result does not depend on
 // how many edges share the call (every row of a tile is an independent k-ordered chain).
 #include "common.h"
-#include "vit_gemm.h"
-#include <math.h>
+#include "mm_tile.h"
 
 namespace {
 
-constexpr int DP_T = 256;
-constexpr int DP_BM = 128;           // pixels of a convolution tile: 4 waves x 32
-constexpr int DP_BK = 32;            // K chunk: 32 channels of one tap
-constexpr int DP_LDA = DP_BK + 4;    // as lpips.hip
+constexpr int DP_T = 256;            // threads of the small kernels
 constexpr int DP_MAX_TOKENS = 4096;
 constexpr int DP_NTAPS = 8;          // intermediates a call leaves in its scratch: L0..L3, path_4..path_1
-
-// element k of a 16-byte vector (hipcc: the vector type's own subscript, which stays in registers; g++: the struct's storage)
-#ifdef __clang__
-#define DP_AT(v, k) ((v)[k])
-#define DP_ATC(v, k) ((v)[k])
-#else
-#define DP_AT(v, k) (((float*)&(v))[k])
-#define DP_ATC(v, k) (((const float*)&(v))[k])
-#endif
-
-struct DpConv {
-  int P;                 // output pixels of the call: edges x Ho x Wo
-  int Hi, Wi, Ho, Wo;    // Ho = ceil(Hi / stride)
-  int Cin, Cout, stride, relu_in;
-};
-
-// The K loop of both convolution kernels: acc[j] += in (x) wt for output columns n0 + 32 j + (0..31) of the tile's 128 pixels,
-// then epilogue(acc).  The accumulators are LOCAL to this function on purpose: handed in by reference from the kernel they cost
-// 50 more VGPRs at NT = 4 (130 + 64 AGPR, 2 waves per SIMD instead of 79 + 64 and 3; the compiler's resource summary).
-template <int NT, class Epilogue>
-__device__ __forceinline__ void dp_conv_loop(const DpConv& g, int n0, const float* __restrict__ in, const float* __restrict__ wt, float* As,
-                                             float* Bs, Epilogue epilogue) {
-  lp_acc16 acc[NT];
-  constexpr int BN = 32 * NT;
-  constexpr int LDB = (BN % 64 == 0) ? BN + 32 : BN;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile0 = blockIdx.x * DP_BM;
-  const int HWo = g.Ho * g.Wo;
-  const int c4 = tid & 7;
-  int base[4], iy[4], ix[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = tile0 + (tid >> 3) + 32 * i;
-    if (p < g.P) {
-      const int e = p / HWo, rem = p - e * HWo, oy = rem / g.Wo, ox = rem - oy * g.Wo;
-      iy[i] = oy * g.stride;
-      ix[i] = ox * g.stride;
-      base[i] = (e * g.Hi + iy[i]) * g.Wi + ix[i];
-    } else {
-      iy[i] = -2;   // every tap of it fails the row test
-      ix[i] = 0;
-      base[i] = 0;
-    }
-  }
-  const int cchunks = g.Cin / DP_BK, nq = 9 * cchunks;
-  lp_f4 ra[4], rb[NT];
-  const lp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  // round q stages chunk q - 1 from registers into LDS, fetches chunk q into registers (in flight under the matrix
-  // instructions) and multiplies chunk q - 1
-  for (int q = 0; q <= nq; ++q) {
-    if (q > 0) {
-      __syncthreads();   // the previous chunk has been consumed
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *(lp_f4*)(As + ((tid >> 3) + 32 * i) * DP_LDA + 4 * c4) = ra[i];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int f = tid + DP_T * j, row = f / (8 * NT), col4 = f - row * (8 * NT);
-        *(lp_f4*)(Bs + row * LDB + 4 * col4) = rb[j];
-      }
-      __syncthreads();
-    }
-    if (q < nq) {
-      const int t = q / cchunks, c0 = (q - t * cchunks) * DP_BK;
-      const int dy = t / 3 - 1, dx = t % 3 - 1;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bool ok = (unsigned)(iy[i] + dy) < (unsigned)g.Hi && (unsigned)(ix[i] + dx) < (unsigned)g.Wi;
-        lp_f4 v = ok ? *(const lp_f4*)(in + (size_t)(base[i] + dy * g.Wi + dx) * g.Cin + c0 + 4 * c4) : zero4;
-        if (g.relu_in) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) DP_AT(v, k) = fmaxf(DP_AT(v, k), 0.f);
-        }
-        ra[i] = v;
-      }
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int f = tid + DP_T * j, row = f / (8 * NT), col4 = f - row * (8 * NT);
-        rb[j] = *(const lp_f4*)(wt + (size_t)(q * DP_BK + row) * g.Cout + n0 + 4 * col4);
-      }
-    }
-    if (q > 0) {
-#pragma unroll 4
-      for (int kk = 0; kk < DP_BK / 2; ++kk)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) lp_mfma_32x32x2(acc[j], As + 32 * wave * DP_LDA + 2 * kk, DP_LDA, Bs + 2 * kk * LDB + 32 * j, LDB, lane);
-    }
-  }
-  epilogue(acc);
-}
 
 // ---------------------------------------------------------------------------------------------------- 3 x 3 convolution
 // grid (ceil(P / 128), Cout / (32 NT)).  in [edge][Hi][Wi][Cin], out [edge][Ho][Wo][Cout]; Cin, Cout multiples of 32; wt
 // [(3 ky + kx) Cin + ci][Cout].  out = r2 + (r1 + (conv + bias)), each of bias, r1, r2 where given (r2 only with r1).
 template <int NT>
-__global__ __launch_bounds__(DP_T) void k_dpt_conv(DpConv g, const float* __restrict__ in, const float* __restrict__ wt,
+__global__ __launch_bounds__(MM_T) void k_dpt_conv(MmConv g, const float* __restrict__ in, const float* __restrict__ wt,
                                                    const float* __restrict__ bias, const float* __restrict__ r1, const float* __restrict__ r2,
                                                    float* __restrict__ out) {
-  constexpr int BN = 32 * NT;
-  constexpr int LDB = (BN % 64 == 0) ? BN + 32 : BN;
-  __shared__ lp_f4 As4[DP_BM * DP_LDA / 4];
-  __shared__ lp_f4 Bs4[DP_BK * LDB / 4];
+  constexpr int LDB = mm_ldb(NT, false);
+  __shared__ lp_f4 As4[MM_BM * MM_LDA / 4];
+  __shared__ lp_f4 Bs4[MM_BK * LDB / 4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tile0 = blockIdx.x * DP_BM, n0 = blockIdx.y * BN;
-  dp_conv_loop<NT>(g, n0, in, wt, (float*)As4, (float*)Bs4, [&](lp_acc16 (&acc)[NT]) {
+  const int tile0 = blockIdx.x * MM_BM, n0 = blockIdx.y * 32 * NT;
+  const MmTapFetch<false> fetch(g, in);
+  mm_k_loop<NT, LDB>(fetch.nq, wt, g.Cout, n0, (float*)As4, (float*)Bs4, fetch, [&](lp_acc16 (&acc)[NT]) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int n = n0 + 32 * j + (lane & 31);
@@ -162,21 +64,19 @@ struct DpPost { float conf_vmin, conf_span; };   // conf = vmin + min(exp(c3), s
 // grid (ceil(P / 128)).  g.Cout = 32 NT = last_dim.  w4: head.4 as [last_dim][32] (columns 4.. zero) then its bias [32].
 // pts3d [P][3], conf [P]; raw4 (may be null) [P][4]: the four channels before postprocess.
 template <int NT>
-__global__ __launch_bounds__(DP_T) void k_dpt_final(DpConv g, DpPost post, const float* __restrict__ in, const float* __restrict__ wt,
+__global__ __launch_bounds__(MM_T) void k_dpt_final(MmConv g, DpPost post, const float* __restrict__ in, const float* __restrict__ wt,
                                                     const float* __restrict__ bias, const float* __restrict__ w4, float* __restrict__ pts3d,
                                                     float* __restrict__ conf, float* __restrict__ raw4) {
-  constexpr int BN = 32 * NT;
-  constexpr int LDB = (BN % 64 == 0) ? BN + 32 : BN;
-  __shared__ lp_f4 As4[DP_BM * DP_LDA / 4];
-  __shared__ lp_f4 Bs4[DP_BK * LDB / 4];   // 32 LDB >= 32 x 32 NT floats: head.4's padded matrix fits
-  float* As = (float*)As4;
-  float* Bs = (float*)Bs4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile0 = blockIdx.x * DP_BM;
-  dp_conv_loop<NT>(g, 0, in, wt, As, Bs, [&](lp_acc16 (&acc)[NT]) {
+  constexpr int BN = 32 * NT, LDB = mm_ldb(NT, false);
+  __shared__ lp_f4 As4[MM_BM * MM_LDA / 4];
+  __shared__ lp_f4 Bs4[MM_BK * LDB / 4];   // 32 LDB >= 32 x 32 NT floats: head.4's padded matrix fits
+  float *As = (float*)As4, *Bs = (float*)Bs4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tile0 = blockIdx.x * MM_BM;
+  const MmTapFetch<true> fetch(g, in);
+  mm_k_loop<NT, LDB>(fetch.nq, wt, g.Cout, 0, As, Bs, fetch, [&](lp_acc16 (&acc)[NT]) {
     __syncthreads();   // the last chunk has been consumed: both tiles are free
-    for (int f = tid; f < BN * 8; f += DP_T) Bs4[f] = ((const lp_f4*)w4)[f];
-    float* Aw = As + 32 * wave * DP_LDA;   // this wave's 32 pixels x 32 channels
+    for (int f = tid; f < BN * 8; f += MM_T) Bs4[f] = ((const lp_f4*)w4)[f];
+    float* Aw = As + 32 * wave * MM_LDA;   // this wave's 32 pixels x 32 channels
     lp_acc16 o;
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[r] = 0.f;
@@ -184,21 +84,21 @@ __global__ __launch_bounds__(DP_T) void k_dpt_final(DpConv g, DpPost post, const
     for (int j = 0; j < NT; ++j) {
       const float bv = bias[32 * j + (lane & 31)];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Aw[lp_acc_row(r, lane) * DP_LDA + (lane & 31)] = fmaxf(acc[j][r] + bv, 0.f);
+      for (int r = 0; r < 16; ++r) Aw[lp_acc_row(r, lane) * MM_LDA + (lane & 31)] = fmaxf(acc[j][r] + bv, 0.f);
       __syncthreads();
 #pragma unroll 4
-      for (int kk = 0; kk < 16; ++kk) lp_mfma_32x32x2(o, Aw + 2 * kk, DP_LDA, Bs + (32 * j + 2 * kk) * 32, 32, lane);
+      for (int kk = 0; kk < 16; ++kk) lp_mfma_32x32x2(o, Aw + 2 * kk, MM_LDA, Bs + (32 * j + 2 * kk) * 32, 32, lane);
       __syncthreads();
     }
     if ((lane & 31) < 4) {
       const float b4 = w4[BN * 32 + (lane & 31)];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Aw[lp_acc_row(r, lane) * DP_LDA + (lane & 31)] = o[r] + b4;
+      for (int r = 0; r < 16; ++r) Aw[lp_acc_row(r, lane) * MM_LDA + (lane & 31)] = o[r] + b4;
     }
     __syncthreads();
     const int p = tile0 + 32 * wave + lane;
     if (lane < 32 && p < g.P) {
-      const float x = Aw[lane * DP_LDA], y = Aw[lane * DP_LDA + 1], z = Aw[lane * DP_LDA + 2], c = Aw[lane * DP_LDA + 3];
+      const float x = Aw[lane * MM_LDA], y = Aw[lane * MM_LDA + 1], z = Aw[lane * MM_LDA + 2], c = Aw[lane * MM_LDA + 3];
       if (raw4) {
         const lp_f4 v = {x, y, z, c};
         *(lp_f4*)(raw4 + (size_t)p * 4) = v;
@@ -251,7 +151,7 @@ __global__ __launch_bounds__(DP_T) void k_dpt_up2(long long total4, int hi, int 
   lp_f4 v;
 #pragma unroll
   for (int k = 0; k < 4; ++k)
-    DP_AT(v, k) = (1.f - ly) * ((1.f - lx) * DP_ATC(a, k) + lx * DP_ATC(b, k)) + ly * ((1.f - lx) * DP_ATC(cc, k) + lx * DP_ATC(d, k));
+    LP_AT(v, k) = (1.f - ly) * ((1.f - lx) * LP_ATC(a, k) + lx * LP_ATC(b, k)) + ly * ((1.f - lx) * LP_ATC(cc, k) + lx * LP_ATC(d, k));
   out[i] = v;
 }
 
@@ -350,15 +250,15 @@ int dp_conv(hipStream_t stream, int E, int Hi, int Wi, int stride, bool relu_in,
             const float* r1, const float* r2, float* out) {
   const int debug = 0;
   const int Ho = (Hi + stride - 1) / stride, Wo = (Wi + stride - 1) / stride;
-  const DpConv g = {E * Ho * Wo, Hi, Wi, Ho, Wo, Cin, Cout, stride, relu_in ? 1 : 0};
+  const MmConv g = {E * Ho * Wo, Hi, Wi, Ho, Wo, Cin, Cout, stride, relu_in ? 1 : 0};
   const float* bias = has_bias ? wt + (size_t)9 * Cin * Cout : nullptr;
   const int nt = dp_conv_nt(Cout);
-  const dim3 grid((unsigned)((g.P + DP_BM - 1) / DP_BM), (unsigned)(Cout / (32 * nt)));
+  const dim3 grid((unsigned)((g.P + MM_BM - 1) / MM_BM), (unsigned)(Cout / (32 * nt)));
   GS_KRANGE("dpt_conv");
   switch (nt) {
-    case 4: hipLaunchKernelGGL(k_dpt_conv<4>, grid, dim3(DP_T), 0, stream, g, in, wt, bias, r1, r2, out); break;
-    case 2: hipLaunchKernelGGL(k_dpt_conv<2>, grid, dim3(DP_T), 0, stream, g, in, wt, bias, r1, r2, out); break;
-    default: hipLaunchKernelGGL(k_dpt_conv<1>, grid, dim3(DP_T), 0, stream, g, in, wt, bias, r1, r2, out); break;
+    case 4: hipLaunchKernelGGL(k_dpt_conv<4>, grid, dim3(MM_T), 0, stream, g, in, wt, bias, r1, r2, out); break;
+    case 2: hipLaunchKernelGGL(k_dpt_conv<2>, grid, dim3(MM_T), 0, stream, g, in, wt, bias, r1, r2, out); break;
+    default: hipLaunchKernelGGL(k_dpt_conv<1>, grid, dim3(MM_T), 0, stream, g, in, wt, bias, r1, r2, out); break;
   }
   GS_CHECK_LAUNCH("dpt_conv");
   return MI355GS_OK;
@@ -495,17 +395,17 @@ int mi355gs_dpt_head(void* stream_, const mi355gs_dpt_config* cfg, const float* 
   DP_TRY(dp_conv(stream, E, 8 * Ht, 8 * Wt, 1, false, F, p.F2, tap[7], w, true, nullptr, nullptr, h0));
   w += dp_lin(9 * F, p.F2);
   DP_TRY(dp_up2(stream, E, 8 * Ht, 8 * Wt, p.H, p.W, p.F2, h0, up));
-  const DpConv g = {E * p.H * p.W, p.H, p.W, p.H, p.W, p.F2, p.LD, 1, 0};
+  const MmConv g = {E * p.H * p.W, p.H, p.W, p.H, p.W, p.F2, p.LD, 1, 0};   // k_dpt_final's MmTapFetch<true> needs Ho = Hi, Wo = Wi, stride 1, no ReLU
   const float* b2 = w + (size_t)9 * p.F2 * p.LD;
   const float* w4 = b2 + p.LD;
   const DpPost post = {cfg->conf_vmin, cfg->conf_vmax - cfg->conf_vmin};
-  const dim3 grid((unsigned)((g.P + DP_BM - 1) / DP_BM));
+  const dim3 grid((unsigned)((g.P + MM_BM - 1) / MM_BM));
   GS_KRANGE("dpt_final");
   switch (p.LD / 32) {
-    case 4: hipLaunchKernelGGL(k_dpt_final<4>, grid, dim3(DP_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
-    case 3: hipLaunchKernelGGL(k_dpt_final<3>, grid, dim3(DP_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
-    case 2: hipLaunchKernelGGL(k_dpt_final<2>, grid, dim3(DP_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
-    default: hipLaunchKernelGGL(k_dpt_final<1>, grid, dim3(DP_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
+    case 4: hipLaunchKernelGGL(k_dpt_final<4>, grid, dim3(MM_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
+    case 3: hipLaunchKernelGGL(k_dpt_final<3>, grid, dim3(MM_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
+    case 2: hipLaunchKernelGGL(k_dpt_final<2>, grid, dim3(MM_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
+    default: hipLaunchKernelGGL(k_dpt_final<1>, grid, dim3(MM_T), 0, stream, g, post, (const float*)up, w, b2, w4, pts3d, conf, raw4); break;
   }
   GS_CHECK_LAUNCH("dpt_final");
   return MI355GS_OK;

@@ -7,27 +7,22 @@
 // so K is contiguous in memory per tap and the packed weights are a plain [K][Cout] matrix.
 //
 //   k_lpips_conv0   bytes -> block 1's first layer.  K = 27: VALU, the normalised 3x3 patches of 64 pixels staged in LDS.
-//   k_lpips_conv    every other layer: 128 pixels x (32, 64, 96 or 128) outputs per workgroup, K in chunks of 32 channels of one
-//                   tap through LDS, v_mfma_f32_32x32x2_f32 (exact float32: a k-ordered fmaf chain), bias + ReLU in the epilogue.
-//                   Border taps are predicated loads that yield zero; nothing outside a buffer is read.
+//   k_lpips_conv    every other layer: 128 pixels x (32, 64, 96 or 128) outputs per workgroup on the shared K loop and tap fetch
+//                   (mm_tile.h: v_mfma_f32_32x32x2_f32, exact float32, a k-ordered fmaf chain), bias + ReLU in the epilogue.
 //   k_lpips_pool    2x2 stride-2 max-pool (floor) in front of blocks 2 to 5.
 //   k_lpips_tap     per pixel of a pair: channel-normalise both, sum_c w_c (xa^ - xb^)^2; per-workgroup partial sums in a fixed order.
 //   k_lpips_finish  per pair: the five spatial means and their sum, fixed order.  No atomics anywhere: equal bits run to run, and
 //                   (a, b) against (b, a) — the difference is squared and every other step treats the two images alike.
 #include "common.h"
+#include "mm_tile.h"
 
 namespace {
 
-constexpr int LP_T = 256;            // threads of every workgroup but the finishing one
-constexpr int LP_BM = 128;           // pixels of a convolution tile: 4 waves x 32
-constexpr int LP_BK = 32;            // K chunk: 32 channels of one tap
-constexpr int LP_LDA = LP_BK + 4;    // LDS row of a pixel's chunk (16-byte aligned rows, rows 16 apart share a bank: 2-way)
+constexpr int LP_T = 256;            // threads of every workgroup but the convolution's (mm_tile.h) and the finishing one
 constexpr int LP_P0 = 64;            // pixels of a first-layer tile
 constexpr int LP_TAP_PIX = 256;      // pixels of a tap workgroup: 4 waves x 64
 constexpr int LP_MAX_C = 512;
 constexpr float LP_EPS = 1e-10f;
-
-// lp_acc16, lp_f4, lp_mfma_32x32x2 and lp_acc_row: common.h (shared with vit.hip)
 
 // ---------------------------------------------------------------------------------------------------- first layer
 // (byte / 255 - mean) / std as the reference's float32 tensor ops round it; the zero padding pads the NORMALISED image.
@@ -72,90 +67,29 @@ __global__ __launch_bounds__(LP_T) void k_lpips_conv0(int N, int H, int W, int C
 
 // ---------------------------------------------------------------------------------------------------- implicit GEMM
 // grid (ceil(P / 128), Cout / (32 NT)).  P = images x H x W flattened pixels of [image][y][x][Cin] input; Cin, Cout multiples of 32.
+// The shared tap fetch at stride 1 without ReLU on the way in (mm_tile.h); bias + ReLU in the epilogue.
 template <int NT>
-__global__ __launch_bounds__(LP_T) void k_lpips_conv(int P, int H, int W, int Cin, int Cout, const float* __restrict__ in,
+__global__ __launch_bounds__(MM_T) void k_lpips_conv(int P, int H, int W, int Cin, int Cout, const float* __restrict__ in,
                                                      const float* __restrict__ wt, const float* __restrict__ bias, float* __restrict__ out) {
-  constexpr int BN = 32 * NT;
-  constexpr int LDB = (BN % 64 == 0) ? BN + 32 : BN;   // rows k and k + 1 half the banks apart: the two lane halves do not collide
-  __shared__ lp_f4 As4[LP_BM * LP_LDA / 4];
-  __shared__ lp_f4 Bs4[LP_BK * LDB / 4];
-  float* As = (float*)As4;
-  float* Bs = (float*)Bs4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile0 = blockIdx.x * LP_BM, n0 = blockIdx.y * BN;
-  const int HW = H * W;
-
-  // the four (pixel, 4-channel group) items this thread stages per chunk, and their place in the image
-  const int c4 = tid & 7;
-  int pp[4], py[4], px[4];
+  constexpr int LDB = mm_ldb(NT, false);
+  __shared__ lp_f4 As4[MM_BM * MM_LDA / 4];
+  __shared__ lp_f4 Bs4[MM_BK * LDB / 4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tile0 = blockIdx.x * MM_BM, n0 = blockIdx.y * 32 * NT;
+  const MmConv g = {P, H, W, H, W, Cin, Cout, 1, 0};
+  const MmTapFetch<true> fetch(g, in);
+  mm_k_loop<NT, LDB>(fetch.nq, wt, Cout, n0, (float*)As4, (float*)Bs4, fetch, [&](lp_acc16 (&acc)[NT]) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = tile0 + (tid >> 3) + 32 * i;
-    pp[i] = p;
-    if (p < P) {
-      const int rem = p % HW;
-      py[i] = rem / W;
-      px[i] = rem - py[i] * W;
-    } else {
-      py[i] = -2;   // every tap of it fails the row test
-      px[i] = 0;
-    }
-  }
-  const int cchunks = Cin / LP_BK, nq = 9 * cchunks;
-  lp_f4 ra[4], rb[NT];
-  const lp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  lp_acc16 acc[NT];
+    for (int j = 0; j < NT; ++j) {
+      const int n = n0 + 32 * j + (lane & 31);
+      const float bv = bias[n];
 #pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-
-  // round q stages chunk q - 1 from registers into LDS, fetches chunk q into registers (in flight under the matrix
-  // instructions) and multiplies chunk q - 1
-  for (int q = 0; q <= nq; ++q) {
-    if (q > 0) {
-      __syncthreads();   // the previous chunk has been consumed
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *(lp_f4*)(As + ((tid >> 3) + 32 * i) * LP_LDA + 4 * c4) = ra[i];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int f = tid + LP_T * j, row = f / (8 * NT), col4 = f - row * (8 * NT);
-        *(lp_f4*)(Bs + row * LDB + 4 * col4) = rb[j];
-      }
-      __syncthreads();
-    }
-    if (q < nq) {
-      const int t = q / cchunks, c0 = (q - t * cchunks) * LP_BK;
-      const int dy = t / 3 - 1, dx = t % 3 - 1;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const bool ok = (unsigned)(py[i] + dy) < (unsigned)H && (unsigned)(px[i] + dx) < (unsigned)W;
-        ra[i] = ok ? *(const lp_f4*)(in + (size_t)(pp[i] + dy * W + dx) * Cin + c0 + 4 * c4) : zero4;
-      }
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int f = tid + LP_T * j, row = f / (8 * NT), col4 = f - row * (8 * NT);
-        rb[j] = *(const lp_f4*)(wt + (size_t)(q * LP_BK + row) * Cout + n0 + 4 * col4);
+      for (int r = 0; r < 16; ++r) {
+        const int p = tile0 + 32 * wave + lp_acc_row(r, lane);
+        if (p < P) out[(size_t)p * Cout + n] = fmaxf(acc[j][r] + bv, 0.f);
       }
     }
-    if (q > 0) {
-#pragma unroll 4
-      for (int kk = 0; kk < LP_BK / 2; ++kk)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) lp_mfma_32x32x2(acc[j], As + 32 * wave * LP_LDA + 2 * kk, LP_LDA, Bs + 2 * kk * LDB + 32 * j, LDB, lane);
-    }
-  }
-
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int n = n0 + 32 * j + (lane & 31);
-    const float bv = bias[n];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int p = tile0 + 32 * wave + lp_acc_row(r, lane);
-      if (p < P) out[(size_t)p * Cout + n] = fmaxf(acc[j][r] + bv, 0.f);
-    }
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------- max-pool
@@ -283,13 +217,13 @@ struct LpPlan {
 int lp_conv(hipStream_t stream, int P, int H, int W, int Cin, int Cout, const float* in, const float* wt, const float* bias, float* out) {
   const int debug = 0;
   const int nt = Cout % 128 == 0 ? 4 : Cout % 96 == 0 ? 3 : Cout % 64 == 0 ? 2 : 1;
-  const dim3 grid((unsigned)((P + LP_BM - 1) / LP_BM), (unsigned)(Cout / (32 * nt)));
+  const dim3 grid((unsigned)((P + MM_BM - 1) / MM_BM), (unsigned)(Cout / (32 * nt)));
   GS_KRANGE("lpips_conv");
   switch (nt) {
-    case 4: hipLaunchKernelGGL(k_lpips_conv<4>, grid, dim3(LP_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
-    case 3: hipLaunchKernelGGL(k_lpips_conv<3>, grid, dim3(LP_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
-    case 2: hipLaunchKernelGGL(k_lpips_conv<2>, grid, dim3(LP_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
-    default: hipLaunchKernelGGL(k_lpips_conv<1>, grid, dim3(LP_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
+    case 4: hipLaunchKernelGGL(k_lpips_conv<4>, grid, dim3(MM_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
+    case 3: hipLaunchKernelGGL(k_lpips_conv<3>, grid, dim3(MM_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
+    case 2: hipLaunchKernelGGL(k_lpips_conv<2>, grid, dim3(MM_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
+    default: hipLaunchKernelGGL(k_lpips_conv<1>, grid, dim3(MM_T), 0, stream, P, H, W, Cin, Cout, in, wt, bias, out); break;
   }
   GS_CHECK_LAUNCH("lpips_conv");
   return MI355GS_OK;

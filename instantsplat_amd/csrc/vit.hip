@@ -5,7 +5,7 @@
 // weights packed [K][N] (torch's weight transposed, once, by the wrapper).
 //
 //   k_vit_patches    planar images -> [token][3 * 16 * 16] rows (k = (c * 16 + py) * 16 + px, the flattened convolution weight)
-//   k_vit_gemm       (vit_gemm.h, shared with dpt.hip) 128 rows x (64 or 128) outputs per workgroup, K in chunks of 32 through LDS, v_mfma_f32_32x32x2_f32 (exact
+//   k_vit_gemm       (mm_tile.h, shared with dpt.hip) 128 rows x (64 or 128) outputs per workgroup, K in chunks of 32 through LDS, v_mfma_f32_32x32x2_f32 (exact
 //                    float32: a k-ordered fmaf chain), epilogue: bias; bias + exact-erf GELU; resid + bias.  Rows past M are never
 //                    loaded or stored.
 //   k_vit_layernorm  a wave per token, the row held in registers: mean, then the sum of squared deviations, fixed lane order.
@@ -17,11 +17,12 @@
 // stream, as the runtime decides for pageable memory); equal bits run to run, and a token's result does not depend on
 // which tile it falls in (every row of a tile is an independent chain).
 #include "common.h"
-#include "vit_gemm.h"
+#include "mm_tile.h"
 #include <math.h>
 
 namespace {
 
+constexpr int VT_T = 256;            // threads of every kernel here (the GEMM's own: mm_tile.h)
 constexpr int VT_HD = 64;            // head dimension
 constexpr int VT_AQ = 64;            // query rows of an attention workgroup
 constexpr int VT_AK = 64;            // keys of a chunk

@@ -272,7 +272,7 @@ def check_case(dev, net, Ht, Wt, E):
     return c, outs
 
 
-# The host's kernel-selection rules (csrc/dpt.hip dp_conv_nt, k_dpt_final's NT, vit_gemm.h vt_gemm<true>), restated.
+# The host's kernel-selection rules (csrc/dpt.hip dp_conv_nt, k_dpt_final's NT, mm_tile.h vt_gemm<true>), restated.
 def conv_nt(cout):
     return 4 if cout % 128 == 0 else 2 if cout % 64 == 0 else 1
 
