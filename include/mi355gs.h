@@ -128,6 +128,35 @@ int mi355gs_raster_backward(
     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dshs_rest, float* dL_dcolors, float* dL_dopacities,
     float* dL_dscales, float* dL_drotations, float* dL_dcov3D, int grad_scratch_is_clear, int debug);
 
+/* Depth and accumulated-alpha maps of a rendered frame, and their backward (added within ABI v10: new entry points only).
+ * Per pixel, over its tile's depth-sorted list with the colour walk's own rules (csrc/composite.hip): T_i the transmittance in
+ * front of entry i, alpha_i = min(0.99, opacity 2^power2), z_i the Gaussian's view depth (the z of viewmatrix applied to its
+ * mean),
+ *     depth = sum_i T_i alpha_i z_i   (the expected depth: NOT divided by alpha, no background term; 0 where nothing blends)
+ *     alpha = 1 - final_T
+ * mi355gs_raster_depth_forward runs after stage 2 of the same frame — mi355gs_raster_forward_render or
+ * mi355gs_raster_forward_render_only, with the same bits after either — on its geom / tiles / binning / capacity (`binning` laid
+ * out under the knobs the frame was made with; only the lists in its head are read).  out_depth[H,W], out_alpha[H,W]: either
+ * may be null.  P = 0 or capacity = 0: both maps are zero.
+ * mi355gs_raster_depth_backward: dL_ddepth[H,W] and dL_dalpha[H,W] in (either may be null: zero), the scene and view arguments
+ * of mi355gs_raster_backward that the chain needs (colours and SH do not enter; the opacity is read from the frame's records), and
+ * gradients out, all written (zero where unused): dL_dmeans3D, dL_dmeans2D, dL_dopacities, dL_dscales + dL_drotations or
+ * dL_dcov3D — to be ADDED to what mi355gs_raster_backward gives for a colour gradient of the same frame.  It may follow either
+ * stage 2.  depth_scratch: mi355gs_raster_depth_scratch_bytes(P) bytes, cleared by the call (per-Gaussian moment records and
+ * dL/dz).  The sums are float atomics: they depend on arrival order, and mi355gs_tune_deterministic does NOT cover this call. */
+int mi355gs_raster_depth_forward(
+    void* stream, int P, int W, int H, int64_t capacity,
+    const void* geom, const void* tiles, const void* binning, float* out_depth, float* out_alpha);
+size_t mi355gs_raster_depth_scratch_bytes(int P);
+int mi355gs_raster_depth_backward(
+    void* stream, int P, int W, int H,
+    const float* means3D, const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* campos, float tanfovx, float tanfovy,
+    const void* geom, const void* tiles, const void* binning, int64_t capacity, const int32_t* radii,
+    const float* dL_ddepth, const float* dL_dalpha, void* depth_scratch,
+    float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacities, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+    int debug);
+
 /* Visibility test only — replaces diff_gaussian_rasterization._C.mark_visible
  * (GaussianRasterizer.markVisible; not called by the reference's scripts). present[P] uint8. */
 int mi355gs_raster_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix,

@@ -34,6 +34,10 @@ _SIGNATURES = {
     "mi355gs_raster_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P,
                                         _P, c_float, c_float, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         c_int, c_int]),
+    "mi355gs_raster_depth_forward": (c_int, [_P, c_int, c_int, c_int, c_int64, _P, _P, _P, _P, _P]),
+    "mi355gs_raster_depth_scratch_bytes": (c_size_t, [c_int]),
+    "mi355gs_raster_depth_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P,
+                                              c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int]),
     "mi355gs_raster_mark_visible": (c_int, [_P, c_int, _P, _P, _P, _P]),
     "mi355gs_raster_frame_stats": (c_int, [_P, c_int, c_int, _P, _P]),
     "mi355gs_tune_min_units": (c_int, [c_int]),

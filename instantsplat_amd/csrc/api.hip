@@ -27,6 +27,11 @@ int gs_launch_composite_bwd(hipStream_t, int, int, int, uint32_t, const uint32_t
 int gs_launch_det_prepare(hipStream_t, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const uint2*, char*, uint32_t*, float*);
 int gs_launch_det_gather(hipStream_t, int, uint32_t, const char*, const float*, GsGrad*);
 int gs_launch_frame_stats(hipStream_t, int, int, int, int, const uint32_t*, const uint32_t*, int64_t*);
+int gs_launch_depth_fwd(hipStream_t, int, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
+                        const uint32_t*, const uint32_t*, float*, float*);
+int gs_launch_depth_bwd(hipStream_t, int, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
+                        const uint32_t*, const uint32_t*, const float*, const float*, GsGrad*, float*);
+int gs_launch_depth_dz(hipStream_t, int, const float*, const float*, float*);
 
 // ---- optional per-kernel timing (HIP events on the launch stream)
 namespace {
@@ -342,6 +347,97 @@ int mi355gs_raster_backward(void* stream, int P, int D, int M, int W, int H, con
                            {W, H, viewmatrix, projmatrix, campos, tanfovx, tanfovy},
                            {const_cast<void*>(geom), tiles, const_cast<void*>(binning), capacity, const_cast<int32_t*>(radii), grad_scratch, gs_knobs()},
                            GsFrameCtx(), bg, out_color, dL_dpix, o, grad_scratch_is_clear != 0, debug);
+}
+
+// ---- depth and accumulated-alpha maps: a pass over the frame's lists beside the colour kernels (composite.hip), and its backward
+namespace {
+struct DepthScratchLayout {   // the depth backward's own accumulators: moment records (colour slots stay zero), dL/dz per Gaussian
+  size_t grads, dz, total;
+  explicit DepthScratchLayout(int P) {
+    const size_t n = P > 0 ? (size_t)P : 1;
+    size_t o = 0;
+    grads = o; o += gs_align(n * sizeof(GsGrad));
+    dz = o; o += gs_align(n * sizeof(float));
+    total = o;
+  }
+};
+}  // namespace
+
+size_t mi355gs_raster_depth_scratch_bytes(int P) { return DepthScratchLayout(P).total; }
+
+int mi355gs_raster_depth_forward(void* stream_, int P, int W, int H, int64_t capacity, const void* geom, const void* tiles,
+                                 const void* binning, float* out_depth, float* out_alpha) {
+  GS_RANGE();
+  hipStream_t stream = (hipStream_t)stream_;
+  const int debug = 0;
+  if (P < 0 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE || !geom || !tiles) return MI355GS_EINVAL;
+  const uint32_t cap = clamp_capacity(capacity);
+  if (cap > 0 && !binning) return MI355GS_EINVAL;
+  const size_t map_bytes = (size_t)W * H * sizeof(float);
+  if (P == 0 || cap == 0) {   // nothing blends anywhere
+    if (out_depth && hipMemsetAsync(out_depth, 0, map_bytes, stream) != hipSuccess) return MI355GS_ELAUNCH;
+    if (out_alpha && hipMemsetAsync(out_alpha, 0, map_bytes, stream) != hipSuccess) return MI355GS_ELAUNCH;
+    return MI355GS_OK;
+  }
+  if (!out_depth && !out_alpha) return MI355GS_OK;
+  const GeomLayout gl(P);
+  const TilesLayout tl(W, H);
+  const BinningLayout bl(capacity, tl.T, gs_knobs());   // (the list's offset does not depend on the knobs)
+  const char* g = (const char*)geom;
+  const char* t = (const char*)tiles;
+  const char* b = (const char*)binning;
+  GS_KRANGE("depth_fwd");
+  gs_launch_depth_fwd(stream, tl.T, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list), (const GsRec*)(g + gl.rec),
+                      (const float*)(t + tl.final_T), (const uint32_t*)(t + tl.n_contrib), (const uint32_t*)(t + tl.order), out_depth, out_alpha);
+  GS_CHECK_LAUNCH("depth_fwd");
+  return MI355GS_OK;
+}
+
+int mi355gs_raster_depth_backward(void* stream_, int P, int W, int H, const float* means3D, const float* scales, float scale_modifier,
+                                  const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                  const float* campos, float tanfovx, float tanfovy, const void* geom, const void* tiles, const void* binning,
+                                  int64_t capacity, const int32_t* radii, const float* dL_ddepth, const float* dL_dalpha, void* depth_scratch,
+                                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacities, float* dL_dscales, float* dL_drotations,
+                                  float* dL_dcov3D, int debug) {
+  GS_RANGE();
+  hipStream_t stream = (hipStream_t)stream_;
+  if (P < 0 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE) return MI355GS_EINVAL;
+  if (!geom || !tiles || !depth_scratch || !viewmatrix || !projmatrix || !campos) return MI355GS_EINVAL;
+  const int use_cov = cov3D_precomp != nullptr;
+  if (P > 0 && (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacities)) return MI355GS_EINVAL;
+  if (P > 0 && !use_cov && (!scales || !rotations || !dL_dscales || !dL_drotations)) return MI355GS_EINVAL;
+  if (P > 0 && use_cov && !dL_dcov3D) return MI355GS_EINVAL;
+  const uint32_t cap = clamp_capacity(capacity);
+  if (cap > 0 && !binning) return MI355GS_EINVAL;
+  if (P == 0) return MI355GS_OK;
+  const GeomLayout gl(P);
+  const TilesLayout tl(W, H);
+  const BinningLayout bl(capacity, tl.T, gs_knobs());
+  const DepthScratchLayout dl(P);
+  const char* g = (const char*)geom;
+  const char* t = (const char*)tiles;
+  const char* b = (const char*)binning;
+  GsGrad* grads = (GsGrad*)((char*)depth_scratch + dl.grads);
+  float* dz = (float*)((char*)depth_scratch + dl.dz);
+  if (hipMemsetAsync(depth_scratch, 0, dl.total, stream) != hipSuccess) return MI355GS_ELAUNCH;
+  if (cap > 0 && (dL_ddepth || dL_dalpha)) {
+    GS_KRANGE("depth_bwd");
+    gs_launch_depth_bwd(stream, tl.T, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list), (const GsRec*)(g + gl.rec),
+                        (const float*)(t + tl.final_T), (const uint32_t*)(t + tl.n_contrib), (const uint32_t*)(t + tl.order), dL_ddepth, dL_dalpha, grads, dz);
+    GS_CHECK_LAUNCH("depth_bwd");
+  }
+  // the moments -> dL/dmean2D, dL/dconic, dL/dopacity -> means, scales, rotations / cov3D: the projection backward in its
+  // precomputed-colour form.  The colour slots of the records are zero, so nothing colour-borne exists: no dL_dcolors is stored.
+  const CamParams cp = make_cam(viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier, W, H);
+  GS_KRANGE("preprocess_bwd");
+  gs_launch_preprocess_bwd(stream, P, 0, 0, means3D, nullptr, nullptr, scales, rotations, 0, use_cov, cp, radii, (const GsRec*)(g + gl.rec),
+                           (const float*)(g + gl.cov3D), (const uint8_t*)(g + gl.clamped), grads, dL_dmeans3D, dL_dmeans2D, nullptr, nullptr,
+                           nullptr, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D, GsPosed(), nullptr, false);
+  GS_CHECK_LAUNCH("preprocess_bwd");
+  GS_KRANGE("depth_dz");
+  gs_launch_depth_dz(stream, P, viewmatrix, dz, dL_dmeans3D);
+  GS_CHECK_LAUNCH("depth_dz");
+  return MI355GS_OK;
 }
 
 int mi355gs_tune_deterministic(int on) {

@@ -744,3 +744,196 @@ int gs_launch_composite_bwd(hipStream_t stream, int gx, int W, int H, uint32_t c
 #undef GS_BWD
   return 0;
 }
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// Depth and accumulated-alpha maps (mi355gs_raster_depth_forward / _backward, include/mi355gs.h): a second pass over the lists a
+// colour forward has walked, beside the colour kernels above and sharing their walk arithmetic (quad_hit, gs_power2, gs_exp2,
+// gs_rcp, ALPHA_MIN).  With T_i the transmittance in front of list entry i, alpha_i its alpha and z_i its view depth (GsRec.q2.w):
+//     depth(p) = sum_i T_i alpha_i z_i  (the expected depth: not divided by alpha, no background term),  alpha(p) = 1 - final_T(p).
+// Both kernels: workgroup = one 16x16 tile, wave = one 8x8 quadrant, the four waves never meet.  A wave stages 64 records at a
+// time in wave-private LDS as two float4 — (x, y, depth, Gaussian index) and q1 —, culls them with the colour forward's quad_hit
+// (one record per lane, a ballot) and walks the set bits.  A pixel blends list position k exactly if k < n_contrib[p] and the
+// colour walk's own tests pass on the colour walk's own bits: below its last contributor a pixel was never finished, so
+// "passes the alpha tests" and "was blended" are the same thing and no T_MIN test is needed.  The wave's stop is the maximum of
+// n_contrib over its quadrant, reduced here: neither qmax nor any other table of the training forward is read, so the pass
+// runs — and gives the same bits — after mi355gs_raster_forward_render and after mi355gs_raster_forward_render_only.
+// ------------------------------------------------------------------------------------------------
+// the wave's staged group: lane i's record as two float4, (x, y, depth, Gaussian index) and q1; only this wave reads it back
+__device__ __forceinline__ void depth_stage(float4 (*__restrict__ recl)[2], int lane, const float4& q0, const float4& q1, float z, uint32_t id) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();   // the previous group's broadcast reads are done
+  recl[lane][0] = make_float4(q0.x, q0.y, z, __uint_as_float(id));
+  recl[lane][1] = q1;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// lane i's record of the group at list position `first` (clamped to the last position the wave walks: no load sits in a branch)
+struct DepthRec { float4 q0, q1; float z; uint32_t id; };
+__device__ __forceinline__ DepthRec depth_fetch(const uint32_t* __restrict__ list, const GsRec* __restrict__ recs, uint32_t start, uint32_t first,
+                                                uint32_t stop, int lane) {
+  DepthRec d;
+  d.id = list[start + min(first + (uint32_t)lane, stop - 1u)];
+  const GsRec* r = recs + d.id;
+  d.q0 = r->q0; d.q1 = r->q1; d.z = r->q2.w;
+  return d;
+}
+
+// `order`: the tile scan's heaviest-first order (the colour forward's): the longest lists start first and the tail of the launch
+// is made of short ones.
+__global__ __launch_bounds__(256) void k_depth_fwd(int gx, int W, int H, uint32_t capacity, const uint32_t* __restrict__ tile_start,
+                                                   const uint32_t* __restrict__ list, const GsRec* __restrict__ recs,
+                                                   const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                                                   const uint32_t* __restrict__ order, float* __restrict__ out_depth, float* __restrict__ out_alpha) {
+  __shared__ float4 s_rec[4][GS_SEG][2];
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tile = (int)min(order[blockIdx.x], gridDim.x - 1u);   // (a permutation of the tiles; clamped: never an address from a bad table)
+  const Quad q = make_quad(tile, gx, W, H);
+  const uint32_t start = min(tile_start[tile], capacity), end = min(tile_start[tile + 1], capacity);
+  const size_t pix = (size_t)min(q.py, H - 1) * W + min(q.px, W - 1);
+  const uint32_t mine = q.inside ? n_contrib[pix] : 0u;           // this pixel blends list positions < mine
+  const uint32_t stop = min(gs_wave_max_u32(mine), end - start);   // the wave's: wave-uniform
+  float4 (*__restrict__ recl)[2] = s_rec[wave];
+  float Tr = 1.0f, depth = 0.0f;
+  DepthRec next = {};
+  if (stop) next = depth_fetch(list, recs, start, 0u, stop, lane);
+  for (uint32_t base = 0; base < stop; base += GS_SEG) {
+    const int cnt = (int)min((uint32_t)GS_SEG, stop - base);
+    const DepthRec cur = next;
+    depth_stage(recl, lane, cur.q0, cur.q1, cur.z, 0u);
+    if (base + GS_SEG < stop) next = depth_fetch(list, recs, start, base + GS_SEG, stop, lane);   // in flight while this group is walked
+    unsigned long long mask = __ballot(lane < cnt && quad_hit(cur.q0, cur.q1, q));
+    while (mask) {
+      const int idx = __ffsll(mask) - 1;
+      mask &= mask - 1;
+      const float4 a0 = recl[idx][0], a1 = recl[idx][1];
+      const float power2 = gs_power2(a0.x - q.f[0], a0.y - q.f[1], a1.x, a1.y, a1.z);
+      const float alpha = fminf(0.99f, a1.w * gs_exp2(power2));
+      const bool valid = base + (uint32_t)idx < mine && power2 <= 0.0f && alpha >= ALPHA_MIN;
+      const float w = valid ? alpha * Tr : 0.0f;
+      depth = fmaf(w, a0.z, depth);
+      Tr -= w;
+    }
+  }
+  if (q.inside) {
+    if (out_depth) out_depth[pix] = depth;
+    if (out_alpha) out_alpha[pix] = 1.0f - final_T[pix];
+  }
+}
+
+// Backward of the two maps: back to front over a tile's WHOLE list — no unit cut and no resume from boundary records, so it needs
+// nothing of the training forward's tables either.  Per pixel, with S_i = sum_{j > i} T_j alpha_j z_j:
+//     dL/dalpha_i = gD (T_i z_i - S_i / (1 - alpha_i)) + gA final_T / (1 - alpha_i),   dL/dz_i += gD T_i alpha_i,
+//     w_i = (opacity_i 2^power2) dL/dalpha_i   (unclamped, the colour backward's convention; 0.99 enters the division only).
+// The sums over the quadrant of w (dx, dy, dx^2, dx dy, dy^2, 1) — the six alpha-borne moments of GsGrad — and of dL/dz cross the
+// wave the way the colour backward's nine do (see RED_PITCH): seven moment-major rows of 64 floats in wave-private LDS, read back
+// by 28 lanes as four ds_read_b128 quarters each, two quad_perm steps — and leave it as ONE float atomic per (wave, Gaussian, sum),
+// never one per lane; a Gaussian no pixel of the quadrant blends costs neither.  The accumulators are a scratch of the call's own
+// (GsGrad[P] with the colour slots left zero, float[P] for dz), cleared by the call.
+// Float atomics: the sums depend on arrival order, and mi355gs_tune_deterministic does NOT cover this kernel.
+__global__ __launch_bounds__(256) void k_depth_bwd(int gx, int W, int H, uint32_t capacity, const uint32_t* __restrict__ tile_start,
+                                                   const uint32_t* __restrict__ list, const GsRec* __restrict__ recs,
+                                                   const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                                                   const uint32_t* __restrict__ order, const float* __restrict__ dL_ddepth,
+                                                   const float* __restrict__ dL_dalpha, GsGrad* __restrict__ grads, float* __restrict__ dz) {
+  __shared__ float4 s_rec[4][GS_SEG][2];
+  __shared__ __attribute__((aligned(16))) float s_red[4][7 * RED_PITCH];
+  const int lane = threadIdx.x & 63;
+  const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tile = (int)min(order[blockIdx.x], gridDim.x - 1u);   // (a permutation of the tiles; clamped: never an address from a bad table)
+  const Quad q = make_quad(tile, gx, W, H);
+  const uint32_t start = min(tile_start[tile], capacity), end = min(tile_start[tile + 1], capacity);
+  const size_t pix = (size_t)min(q.py, H - 1) * W + min(q.px, W - 1);
+  const uint32_t mine = q.inside ? n_contrib[pix] : 0u;
+  const uint32_t stop = min(gs_wave_max_u32(mine), end - start);
+  if (stop == 0u) return;   // wave-uniform; no workgroup barrier below
+  const float Tfin = final_T[pix];
+  const float gD = (dL_ddepth && q.inside) ? dL_ddepth[pix] : 0.0f;
+  const float gAT = (dL_dalpha && q.inside) ? dL_dalpha[pix] * Tfin : 0.0f;   // gA final_T
+  float4 (*__restrict__ recl)[2] = s_rec[wave];
+  float* __restrict__ red = s_red[wave];
+  float Tr = Tfin, S = 0.0f;
+  const int last_chunk = (int)((stop - 1u) / GS_SEG);
+  DepthRec next = depth_fetch(list, recs, start, (uint32_t)last_chunk * GS_SEG, stop, lane);
+  for (int c = last_chunk; c >= 0; --c) {
+    const uint32_t base = (uint32_t)c * GS_SEG;
+    const int cnt = (int)min((uint32_t)GS_SEG, stop - base);
+    const DepthRec cur = next;
+    depth_stage(recl, lane, cur.q0, cur.q1, cur.z, cur.id);
+    if (c > 0) next = depth_fetch(list, recs, start, base - GS_SEG, stop, lane);   // in flight while this chunk is walked
+    unsigned long long mask = __ballot(lane < cnt && quad_hit(cur.q0, cur.q1, q));
+    while (mask) {
+      const int idx = 63 - __clzll((long long)mask);   // the deepest remaining one
+      mask &= ~(1ull << idx);
+      const float4 a0 = recl[idx][0], a1 = recl[idx][1];
+      const float dx = a0.x - q.f[0], dy = a0.y - q.f[1];
+      const float power2 = gs_power2(dx, dy, a1.x, a1.y, a1.z);
+      const float au = a1.w * gs_exp2(power2);   // unclamped; inf where power2 > 0: such lanes are invalid and selected away
+      const bool valid = base + (uint32_t)idx < mine && power2 <= 0.0f && au >= ALPHA_MIN;
+      if (!__any(valid)) continue;
+      // a lane that skips this Gaussian treats it as transparent: T and S then evolve as if it were not there
+      const float av = valid ? au : 0.0f;
+      const float al = __builtin_amdgcn_fmed3f(av, 0.0f, 0.99f);   // the colour backward's clamp (ALPHA_MAX_BWD)
+      const float inv_one_m = gs_rcp(1.0f - al);
+      Tr = Tr * inv_one_m;                                           // transmittance in front of this Gaussian
+      const float dL_dal = gD * (Tr * a0.z - S * inv_one_m) + gAT * inv_one_m;
+      const float dchannel = al * Tr;
+      S = fmaf(a0.z, dchannel, S);
+      const float w = av * dL_dal;
+      const float wdx = w * dx, wdy = w * dy;
+      // (LDS operations of one wave execute in program order; the fences keep the compiler from reordering across lanes' accesses)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      red[0 * RED_PITCH + lane] = wdx; red[1 * RED_PITCH + lane] = wdy; red[2 * RED_PITCH + lane] = wdx * dx;
+      red[3 * RED_PITCH + lane] = wdx * dy; red[4 * RED_PITCH + lane] = wdy * dy; red[5 * RED_PITCH + lane] = w;
+      red[6 * RED_PITCH + lane] = gD * dchannel;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      float part = 0.f;
+      if (lane < 28) {
+        const float4* r4 = reinterpret_cast<const float4*>(red + (lane >> 2) * RED_PITCH + (lane & 3) * 16);
+        const float4 a = r4[0], b = r4[1], c4 = r4[2], d = r4[3];
+        part = (((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w))) + (((c4.x + c4.y) + (c4.z + c4.w)) + ((d.x + d.y) + (d.z + d.w)));
+      }
+      part += gs_dpp<0xB1>(part);   // quad_perm [1,0,3,2]
+      part += gs_dpp<0x4E>(part);   // quad_perm [2,3,0,1]: every lane of the quad holds its sum over the wave
+      // lanes 0, 4, .., 20 add moments 0 .. 5, the first six floats of the Gaussian's record; lane 24 adds dL/dz
+      const uint32_t g = __float_as_uint(a0.w);
+      const int k = lane >> 2;
+      if ((lane & 3) == 0 && lane < 28) atomicAdd(k < 6 ? reinterpret_cast<float*>(grads + g) + k : dz + g, part);
+    }
+  }
+}
+
+// dL/dmeans3D += dL/dz (view[2], view[6], view[10]): z is the third row of transformPoint4x3 (k_preprocess_fwd: rec.q2.w = pv.z)
+__global__ __launch_bounds__(256) void k_depth_dz(int P, const float* __restrict__ view, const float* __restrict__ dz, float* __restrict__ dL_dmeans3D) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  const float g = dz[i];
+  dL_dmeans3D[3 * (size_t)i] += g * view[2];
+  dL_dmeans3D[3 * (size_t)i + 1] += g * view[6];
+  dL_dmeans3D[3 * (size_t)i + 2] += g * view[10];
+}
+
+}  // namespace
+
+int gs_launch_depth_fwd(hipStream_t stream, int T, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start, const uint32_t* list,
+                        const GsRec* recs, const float* final_T, const uint32_t* n_contrib, const uint32_t* order, float* out_depth, float* out_alpha) {
+  hipLaunchKernelGGL(k_depth_fwd, dim3(T), dim3(256), 0, stream, gx, W, H, capacity, tile_start, list, recs, final_T, n_contrib, order, out_depth, out_alpha);
+  return 0;
+}
+int gs_launch_depth_bwd(hipStream_t stream, int T, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start, const uint32_t* list,
+                        const GsRec* recs, const float* final_T, const uint32_t* n_contrib, const uint32_t* order, const float* dL_ddepth,
+                        const float* dL_dalpha, GsGrad* grads, float* dz) {
+  hipLaunchKernelGGL(k_depth_bwd, dim3(T), dim3(256), 0, stream, gx, W, H, capacity, tile_start, list, recs, final_T, n_contrib, order, dL_ddepth,
+                     dL_dalpha, grads, dz);
+  return 0;
+}
+int gs_launch_depth_dz(hipStream_t stream, int P, const float* view, const float* dz, float* dL_dmeans3D) {
+  if (P <= 0) return 0;
+  hipLaunchKernelGGL(k_depth_dz, dim3((P + 255) / 256), dim3(256), 0, stream, P, view, dz, dL_dmeans3D);
+  return 0;
+}

@@ -512,6 +512,59 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return color, radii
 
 
+class _RasterizeGaussiansDepth(torch.autograd.Function):
+    """`_RasterizeGaussians` plus the frame's depth and accumulated-alpha maps (include/mi355gs.h, mi355gs_raster_depth_*): the
+    same frame, one more pass over its lists; in the backward the colour chain and the depth chain run only for the gradients
+    that arrived, and their per-Gaussian gradients are added."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None):
+        color, radii = _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                                   raster_settings, sh_rest)
+        ctx.set_materialize_grads(False)
+        geom, tiles, binning = ctx.to_save[8:11]
+        P, _, _, W, H = ctx.dims
+        dev = color.device
+        depth, alpha = (torch.empty(1, H, W, dtype=torch.float32, device=dev) for _ in range(2))
+        with _lib.on_device(dev):
+            _lib.check(_lib.lib().mi355gs_raster_depth_forward(_lib.stream_ptr(dev), P, W, H, int(ctx.num_rendered), _lib.ptr(geom), _lib.ptr(tiles),
+                                                               _lib.ptr(binning), _lib.ptr(depth), _lib.ptr(alpha)), "raster_depth_forward")
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
+        out = [None] * 10
+        if grad_color is not None:
+            out = list(_RasterizeGaussians.backward(ctx, grad_color, None))
+        if grad_depth is None and grad_alpha is None:
+            return tuple(out)
+        s = ctx.raster_settings
+        L = _lib.lib()
+        P, _, _, W, H = ctx.dims
+        means3D, _, _, _, sc_, rot_, cov_, radii, geom, tiles, binning, _, view, proj, campos, _ = ctx.saved_tensors
+        opt = lambda t: None if t.numel() == 0 else t
+        sc_, rot_, cov_ = opt(sc_), opt(rot_), opt(cov_)
+        dev = means3D.device
+        gD, gA = (None if g is None else _lib.f32c(g) for g in (grad_depth, grad_alpha))
+        _lib.require_device(gD, gA)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        d_means3D, d_means2D, d_opac = new(P, 3), new(P, 3), new(P)
+        d_scales, d_rot, d_cov = (new(P, 3), new(P, 4), None) if cov_ is None else (None, None, new(P, 6))
+        scratch = _empty_bytes(L.mi355gs_raster_depth_scratch_bytes(P), dev)
+        with _lib.on_device(dev):
+            _lib.check(L.mi355gs_raster_depth_backward(
+                _lib.stream_ptr(dev), P, W, H, _lib.ptr(means3D), _lib.ptr(sc_), float(s.scale_modifier), _lib.ptr(rot_), _lib.ptr(cov_),
+                _lib.ptr(view), _lib.ptr(proj), _lib.ptr(campos), float(s.tanfovx), float(s.tanfovy), _lib.ptr(geom), _lib.ptr(tiles),
+                _lib.ptr(binning), int(ctx.num_rendered), _lib.ptr(radii), _lib.ptr(gD), _lib.ptr(gA), _lib.ptr(scratch), _lib.ptr(d_means3D),
+                _lib.ptr(d_means2D), _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rot), _lib.ptr(d_cov), 1 if s.debug else 0),
+                "raster_depth_backward")
+        mine = {0: d_means3D, 1: d_means2D, 4: d_opac.reshape(ctx.opacity_shape), 5: d_scales, 6: d_rot, 7: d_cov}
+        for k, g in mine.items():
+            if g is not None:
+                out[k] = g if out[k] is None else out[k] + g
+        return tuple(out)
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
@@ -542,3 +595,21 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(means3D, means2D, e if shs is None else shs, e if colors_precomp is None else colors_precomp,
                                    opacities, e if scales is None else scales, e if rotations is None else rotations,
                                    e if cov3D_precomp is None else cov3D_precomp, raster_settings, shs_rest)
+
+    def forward_depth(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                      cov3D_precomp=None, shs_rest=None):
+        """`forward` with two more outputs: -> (color[3,H,W], radii[P], depth[1,H,W], alpha[1,H,W]).  depth is the EXPECTED depth
+        sum_i T_i alpha_i z_i over the Gaussians a pixel blends (z: view depth; not divided by alpha, no background term), alpha
+        the accumulated opacity 1 - final_T.  Colour and radii are `forward`'s bits.  Gradients flow through all three maps; the
+        depth and alpha gradients are summed with float atomics and are not covered by `set_deterministic`.  One autograd node on
+        the ctypes binding whichever binding `forward` uses; under no_grad it takes the render-only stage 2."""
+        if (shs is None) == (colors_precomp is None):
+            raise Exception("Please provide excatly one of either SHs or precomputed colors!")
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        e = torch.Tensor([])
+        args = (means3D, means2D, e if shs is None else shs, e if colors_precomp is None else colors_precomp, opacities,
+                e if scales is None else scales, e if rotations is None else rotations, e if cov3D_precomp is None else cov3D_precomp)
+        with backward_follows(*args, shs_rest):
+            return _RasterizeGaussiansDepth.apply(*args, self.raster_settings, shs_rest)

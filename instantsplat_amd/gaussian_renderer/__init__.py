@@ -119,3 +119,31 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             means2D=screenspace_points,
             **_operator_inputs(viewpoint_camera, pc, pipe, camera_pose, scaling_modifier, override_color, dev))
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+
+
+def render_depth(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, camera_pose=None):
+    """`render` plus the frame's depth and accumulated-alpha maps: its dict with "depth" and "alpha" added, both [1,H,W]
+    (GaussianRasterizer.forward_depth: the expected depth sum_i T_i alpha_i z_i in the camera frame, and 1 - final_T).  Gradients
+    of a loss on either map reach the Gaussians and `camera_pose` through the same autograd glue as the image's: the pose /
+    activation node and the SH view of the default pipeline, the op-by-op glue for the python-flag variants."""
+    xyz = pc.get_xyz
+    dev = xyz.device
+    screenspace_points = _zero_leaf(xyz)
+    view_identity, origin = _identity_view(dev)
+    projmatrix = viewpoint_camera.projection_matrix
+    if projmatrix.device != dev:
+        projmatrix = projmatrix.to(dev)
+    settings = GaussianRasterizationSettings(
+        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
+        scale_modifier=scaling_modifier, viewmatrix=view_identity, projmatrix=projmatrix, sh_degree=pc.active_sh_degree,
+        campos=origin, prefiltered=False, debug=pipe.debug)
+    if override_color is None and not (pipe.compute_cov3D_python or pipe.convert_SHs_python):
+        means3D, rot_cam, scales_act, opacity = pose_activations(pc._xyz, pc._rotation, pc._scaling, pc._opacity, camera_pose)
+        shs_dc, shs_rest = sh_features(pc)
+        kw = dict(means3D=means3D, shs=shs_dc, opacities=opacity, scales=scales_act, rotations=rot_cam, shs_rest=shs_rest)
+    else:
+        kw = _operator_inputs(viewpoint_camera, pc, pipe, camera_pose, scaling_modifier, override_color, dev)
+    image, radii, depth, alpha = GaussianRasterizer(raster_settings=settings).forward_depth(means2D=screenspace_points, **kw)
+    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii, "depth": depth,
+            "alpha": alpha}
