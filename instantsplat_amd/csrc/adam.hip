@@ -206,7 +206,6 @@ int gs_adam_multi(hipStream_t stream, int ntensors, const int64_t* numel, const 
                   const float* lr, float beta1, float beta2, float eps, const int32_t* step, float* scratch, const float* gate,
                   const int32_t* gate_index, uint32_t* live, uint32_t seq, const GsAdamFused* fused) {
   GsRange range("mi355gs_adam_multi_step");
-  const int debug = 0;
   if (ntensors < 0 || ntensors > MT_MAX || (gate && !gate_index) || (fused && (gate || !scratch))) return MI355GS_EINVAL;
   if (ntensors == 0) return MI355GS_OK;
   if (!numel || !row || !params || !grads || !exp_avg || !exp_avg_sq || !per_point_lr || !lr || !step) return MI355GS_EINVAL;
@@ -307,7 +306,6 @@ extern "C" int mi355gs_adam_step(void* stream_, int64_t n, int row, float* param
                                  float beta2, float eps, int step) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (n < 0 || row <= 0 || step <= 0 || (n > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) return MI355GS_EINVAL;
   if (n == 0) return MI355GS_OK;
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);

@@ -512,7 +512,6 @@ StepArgs step_args(const Align* a, float* depth_log) {
 
 // one iteration's three launches (or, with f.loss_out null, the prepare launch alone)
 int launch_iteration(const Align* a, hipStream_t stream, const StepArgs& s, const FinishArgs& f) {
-  const int debug = 0;
   if (f.loss_out) {
     GS_KRANGE("align_step");
     hipLaunchKernelGGL(k_align_step, dim3(a->nwg, a->V), dim3(256), 0, stream, s);
@@ -586,7 +585,6 @@ int mi355gs_align_pack(void* handle, void* stream_, const float* pred_i, const f
   GS_RANGE();
   Align* a = (Align*)handle;
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!a || !pred_i || !pred_j || !conf_i || !conf_j) return MI355GS_EINVAL;
   int rc;
   if ((rc = upload_tables(a, stream))) return rc;
@@ -649,7 +647,6 @@ int mi355gs_align_points(void* handle, void* stream_, const float* depth_log, co
   GS_RANGE();
   Align* a = (Align*)handle;
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!a || !depth_log || !im_pose || !focal_log || !pp_raw || !pw_pose || !pts3d || !depth) return MI355GS_EINVAL;
   int rc;
   if ((rc = upload_tables(a, stream))) return rc;

@@ -458,7 +458,6 @@ size_t mi355gs_align_init_workspace_bytes(int B, int n) {
 int mi355gs_align_init_means(void* workspace, void* stream_, int rows, int n, const float* x, float* means) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!workspace || !x || !means || !init_size_ok(rows, n)) return MI355GS_EINVAL;
   InitWs w;
   carve(w, workspace, rows, n);
@@ -477,7 +476,6 @@ int mi355gs_align_init_register(void* workspace, void* stream_, int B, int n, co
                                 const int32_t* w_idx, long long w_job_stride, float* srt, float* pw_pose) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!workspace || !src || !tgt || !srt || !init_size_ok(B, n)) return MI355GS_EINVAL;
   if (src_pt_stride < 3 || src_pt_stride > 4 || src_job_stride < 0 || tgt_job_stride < 0 || w_job_stride < 0) return MI355GS_EINVAL;
   InitWs w;
@@ -506,7 +504,6 @@ int mi355gs_align_init_register(void* workspace, void* stream_, int B, int n, co
 int mi355gs_align_init_apply(void* stream_, int n, const float* src, int src_pt_stride, const float* srt, float* dst) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!src || !dst || !init_size_ok(1, n) || src_pt_stride < 3 || src_pt_stride > 4) return MI355GS_EINVAL;
   GS_KRANGE("align_init_apply");
   hipLaunchKernelGGL(k_init_apply, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, src, src_pt_stride, srt, dst);
@@ -518,7 +515,6 @@ int mi355gs_align_init_focals(void* workspace, void* stream_, int B, int H, int 
                               long long src_job_stride, int src_pt_stride, float* focals) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!workspace || !src || !focals || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL || !init_size_ok(B, H * W)) return MI355GS_EINVAL;
   if (src_pt_stride < 3 || src_pt_stride > 4 || src_job_stride < 0) return MI355GS_EINVAL;
   const int n = H * W, nchunk = chunks_of(n);
@@ -541,7 +537,6 @@ int mi355gs_align_init_state(void* workspace, void* stream_, int V, int E, int H
                              const float* pw_pose, float* pts3d, float* depth_log, float* im_pose, float* focal_log) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!workspace || !srt || !pose_row || !focals || !focal_row || !pw_pose || !pts3d || !depth_log || !im_pose || !focal_log) return MI355GS_EINVAL;
   if (V <= 0 || V > MAX_VIEWS || E <= 0 || E > MAX_JOBS || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL || !init_size_ok(V, H * W))
     return MI355GS_EINVAL;

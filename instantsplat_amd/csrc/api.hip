@@ -5,34 +5,6 @@
 #include <dlfcn.h>
 #include <cstdlib>
 
-// launchers implemented next to their kernels
-int gs_launch_preprocess_fwd(hipStream_t, int, int, int, const float*, const float*, const float*, const float*, const float*, const float*,
-                             const float*, const float*, const CamParams&, int32_t*, GsRec*, float*, uint2*, uint8_t*, float*, uint8_t*,
-                             const GsPosed&, const GsPrologue&);
-int gs_launch_count_tiles(hipStream_t, int, int, int, const uint2*, uint32_t*, uint32_t*, uint32_t*);
-int gs_launch_preprocess_bwd(hipStream_t, int, int, int, const float*, const float*, const float*, const float*, const float*, int, int,
-                             const CamParams&, const int32_t*, const GsRec*, const float*, const uint8_t*, const GsGrad*, float*, float*,
-                             float*, float*, float*, float*, float*, float*, float*, const GsPosed&, float*, bool);
-int gs_launch_mark_visible(hipStream_t, int, const float*, const float*, uint8_t*);
-int gs_launch_scan_tiles(hipStream_t, int, const uint32_t*, uint32_t*, int32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, int);
-int gs_launch_binning(hipStream_t, int, int, int, const float*, const uint2*, const uint32_t*, uint32_t*, uint64_t*, uint32_t*, uint32_t,
-                      const uint32_t*, const uint32_t*, const uint32_t*);
-int gs_launch_composite_fwd(hipStream_t, int, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
-                            float*, float*, uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint4*, float4*, uint32_t,
-                            const uint32_t*, unsigned long long*, uint32_t, uint32_t*, unsigned long long*, bool);
-int gs_launch_composite_bwd(hipStream_t, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
-                            const float*, const uint32_t*, const float*, GsGrad*, const float*, const uint4*,
-                            const float4*, const uint32_t*, uint32_t, bool, const unsigned long long*, uint32_t, const uint32_t*,
-                            unsigned long long*, const uint32_t*, float*);
-int gs_launch_det_prepare(hipStream_t, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const uint2*, char*, uint32_t*, float*);
-int gs_launch_det_gather(hipStream_t, int, uint32_t, const char*, const float*, GsGrad*);
-int gs_launch_frame_stats(hipStream_t, int, int, int, int, const uint32_t*, const uint32_t*, int64_t*);
-int gs_launch_depth_fwd(hipStream_t, int, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
-                        const uint32_t*, const uint32_t*, float*, float*);
-int gs_launch_depth_bwd(hipStream_t, int, int, int, int, uint32_t, const uint32_t*, const uint32_t*, const GsRec*, const float*,
-                        const uint32_t*, const uint32_t*, const float*, const float*, GsGrad*, float*);
-int gs_launch_depth_dz(hipStream_t, int, const float*, const float*, float*);
-
 // ---- optional per-kernel timing (HIP events on the launch stream)
 namespace {
 constexpr int PROF_KINDS = 6, PROF_MAX = 8192;   // include/mi355gs.h, mi355gs_profile_read: composite forward / backward / render-only
@@ -114,8 +86,6 @@ static CamParams make_cam(const float* view, const float* proj, const float* cam
   return cp;
 }
 
-static inline uint32_t clamp_capacity(int64_t c) { return c <= 0 ? 0u : (c > 0x7fffffffLL ? 0x7fffffffu : (uint32_t)c); }
-
 // the handles' device constants (common.h)
 namespace {
 __global__ void k_view_consts(float* consts) {
@@ -125,7 +95,6 @@ __global__ void k_view_consts(float* consts) {
 }
 }  // namespace
 int gs_write_view_consts(hipStream_t stream, float* consts, const char* name) {
-  const int debug = 0;
   GS_KRANGE(name);
   hipLaunchKernelGGL(k_view_consts, dim3(1), dim3(64), 0, stream, consts);
   GS_CHECK_LAUNCH(name);
@@ -140,17 +109,14 @@ int gs_frame_project(hipStream_t stream, const GsScene& sc, const GsView& vw, co
                      int32_t* num_rendered, uint8_t* visible, int debug) {
   GsRange range("mi355gs_raster_forward_preprocess");
   const int P = sc.P, D = sc.D, M = sc.M, W = vw.W, H = vw.H;
-  if (P < 0 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE || D < 0 || D > 3) return MI355GS_EINVAL;
+  if (P < 0 || !gs_frame_size_ok(W, H) || D < 0 || D > 3) return MI355GS_EINVAL;
   if (!fb.geom || !fb.tiles || !num_rendered || !vw.view || !vw.proj || !vw.campos) return MI355GS_EINVAL;
   if (P > 0 && (!sc.means3D || !sc.opacities || !fb.radii)) return MI355GS_EINVAL;
   if (P > 0 && ((sc.shs == nullptr) == (sc.colors_precomp == nullptr))) return MI355GS_EINVAL;
   if (P > 0 && sc.shs && M < (D + 1) * (D + 1)) return MI355GS_EINVAL;
   if (sc.shs_rest && (!sc.shs || M < 2)) return MI355GS_EINVAL;
   if (P > 0 && !sc.cov3D_precomp && (!sc.scales || !sc.rotations)) return MI355GS_EINVAL;
-  const GeomLayout gl(P);
-  const TilesLayout tl(W, H);
-  char* g = (char*)fb.geom;
-  char* t = (char*)fb.tiles;
+  const GsFrame f({fb.geom, fb.tiles, nullptr, 0, fb.radii, fb.grad_scratch, fb.knobs}, P, W, H);   // no stage-1 kernel touches `binning`
   // The frame's accumulators are cleared by the projection kernel on its way (a fused caller hands over its own list): the
   // per-tile count + cursor words (adjacent), and — if the caller already holds the buffer its backward will use — the moment
   // records with the gate flags behind them.  No Gaussians, no kernel: memsets then.
@@ -158,28 +124,23 @@ int gs_frame_project(hipStream_t stream, const GsScene& sc, const GsView& vw, co
   if (cx.prologue) {
     pro = *cx.prologue;
   } else {
-    pro.tile_counters = (uint32_t*)(t + tl.count); pro.n_counters = (int)((tl.start - tl.count) / 4);
+    pro.tile_counters = f.count; pro.n_counters = f.n_counters;
     if (fb.grad_scratch) { pro.grad_records = (float4*)fb.grad_scratch; pro.n_vec = gs_grad_gate_offset(P) / 16 + 2; }
     if (P <= 0) {
-      if (hipMemsetAsync(t + tl.count, 0, tl.start - tl.count, stream) != hipSuccess) return MI355GS_ELAUNCH;
+      if (hipMemsetAsync(f.count, 0, (size_t)f.n_counters * 4, stream) != hipSuccess) return MI355GS_ELAUNCH;
       if (fb.grad_scratch && hipMemsetAsync(fb.grad_scratch, 0, gs_grad_gate_offset(P) + 32, stream) != hipSuccess) return MI355GS_ELAUNCH;
     }
   }
   const CamParams cp = make_cam(vw.view, vw.proj, vw.campos, vw.tanfovx, vw.tanfovy, sc.scale_modifier, W, H);
   GS_KRANGE("preprocess_fwd");
-  gs_launch_preprocess_fwd(stream, P, D, M, sc.means3D, sc.shs, sc.shs_rest, sc.colors_precomp, sc.opacities, sc.scales, sc.rotations,
-                           sc.cov3D_precomp, cp, fb.radii, (GsRec*)(g + gl.rec), (float*)(g + gl.cov3D), (uint2*)(g + gl.rect),
-                           (uint8_t*)(g + gl.clamped), (float*)(g + gl.depth), visible, cx.posed, pro);
-  GS_CHECK_LAUNCH("preprocess_fwd");
+  gs_launch_preprocess_fwd(stream, sc, cp, f, visible, cx.posed, pro);
+  GS_CHECK_LAUNCH_SYNC("preprocess_fwd", stream, debug);
   GS_KRANGE("count_tiles");
-  gs_launch_count_tiles(stream, P, tl.T, tl.gx, (const uint2*)(g + gl.rect), (uint32_t*)(t + tl.count), (uint32_t*)(g + gl.bin_entries),
-                        (uint32_t*)(g + gl.bin_n));
-  GS_CHECK_LAUNCH("count_tiles");
+  gs_launch_count_tiles(stream, f);
+  GS_CHECK_LAUNCH_SYNC("count_tiles", stream, debug);
   GS_KRANGE("scan_tiles");
-  gs_launch_scan_tiles(stream, tl.T, (const uint32_t*)(t + tl.count), (uint32_t*)(t + tl.start), num_rendered,
-                       (uint32_t*)(t + tl.order), (uint32_t*)(t + tl.meta), (uint32_t*)(t + tl.seg_first), (uint32_t*)(t + tl.part_first),
-                       fb.knobs.min_units);
-  GS_CHECK_LAUNCH("scan_tiles");
+  gs_launch_scan_tiles(stream, f, num_rendered, fb.knobs.min_units);
+  GS_CHECK_LAUNCH_SYNC("scan_tiles", stream, debug);
   return MI355GS_OK;
 }
 
@@ -190,31 +151,17 @@ int gs_frame_render(hipStream_t stream, int P, const GsView& vw, const GsFrameBu
   GsRange range(train ? "mi355gs_raster_forward_render" : "mi355gs_raster_forward_render_only");
   const int W = vw.W, H = vw.H;
   if (P < 0 || W <= 0 || H <= 0 || !fb.geom || !fb.tiles || !bg || !out_color) return MI355GS_EINVAL;
-  const uint32_t cap = clamp_capacity(fb.capacity);
-  if (cap > 0 && !fb.binning) return MI355GS_EINVAL;
-  const GeomLayout gl(P);
-  const TilesLayout tl(W, H);
-  const BinningLayout bl(fb.capacity, tl.T, fb.knobs);   // (keys and list come first in it: the render-only buffer is its head)
-  const char* g = (const char*)fb.geom;
-  char* t = (char*)fb.tiles;
-  char* b = (char*)fb.binning;
+  if (clamp_capacity(fb.capacity) > 0 && !fb.binning) return MI355GS_EINVAL;
+  const GsFrame f(fb, P, W, H);
   GS_KRANGE("binning");
-  gs_launch_binning(stream, P, tl.T, tl.gx, (const float*)(g + gl.depth), (const uint2*)(g + gl.rect),
-                    (const uint32_t*)(t + tl.start), (uint32_t*)(t + tl.cursor), (uint64_t*)(b + bl.keys),
-                    (uint32_t*)(b + bl.list), cap, (const uint32_t*)(t + tl.order), (const uint32_t*)(g + gl.bin_entries),
-                    (const uint32_t*)(g + gl.bin_n));
-  GS_CHECK_LAUNCH("binning");
+  gs_launch_binning(stream, f);
+  GS_CHECK_LAUNCH_SYNC("binning", stream, debug);
   {
     ProfScope prof(train ? 0 : 2, stream);
     GS_KRANGE("composite_fwd");
-    gs_launch_composite_fwd(stream, tl.T, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list),
-                            (const GsRec*)(g + gl.rec), bg, out_color, (float*)(t + tl.final_T), (uint32_t*)(t + tl.n_contrib),
-                            (const uint32_t*)(t + tl.order), (const uint32_t*)(t + tl.seg_first), (const uint32_t*)(t + tl.part_first),
-                            train ? (uint4*)(b + bl.unit_tile) : nullptr, train ? (float4*)(b + bl.bstate) : nullptr, bl.max_units,
-                            (const uint32_t*)(t + tl.meta), train ? (unsigned long long*)(b + bl.hitmask) : nullptr, bl.max_chunks,
-                            (uint32_t*)(t + tl.qmax), train ? g_prof.work_counters : nullptr, train);
+    gs_launch_composite_fwd(stream, f, bg, out_color, train ? g_prof.work_counters : nullptr, train);
   }
-  GS_CHECK_LAUNCH("composite_fwd");
+  GS_CHECK_LAUNCH_SYNC("composite_fwd", stream, debug);
   return MI355GS_OK;
 }
 
@@ -234,56 +181,39 @@ int gs_frame_backward(hipStream_t stream, const GsScene& sc, const GsView& vw, c
   if (P > 0 && !use_cov && (!sc.scales || !sc.rotations || (outs && (!o.scales || !o.rotations)))) return MI355GS_EINVAL;
   if (P > 0 && outs && use_cov && !o.cov3D) return MI355GS_EINVAL;
   if (P == 0) return MI355GS_OK;
-  const uint32_t cap = clamp_capacity(fb.capacity);
-  if (cap > 0 && !fb.binning) return MI355GS_EINVAL;
-  const GeomLayout gl(P);
-  const TilesLayout tl(W, H);
-  const BinningLayout bl(fb.capacity, tl.T, fb.knobs);
-  const char* g = (const char*)fb.geom;
-  const char* t = (const char*)fb.tiles;
-  char* b = (char*)fb.binning;
+  if (clamp_capacity(fb.capacity) > 0 && !fb.binning) return MI355GS_EINVAL;
+  const GsFrame f(fb, P, W, H);
   GsGrad* grads = (GsGrad*)fb.grad_scratch;
   // (with gate_tail the eight gate flags behind the records are cleared by the same memset)
   const size_t clear_bytes = cx.gate_tail ? gs_grad_gate_offset(P) + 8 * sizeof(float) : (size_t)P * sizeof(GsGrad);
   if (!cx.prologue && !grad_scratch_is_clear && hipMemsetAsync(grads, 0, clear_bytes, stream) != hipSuccess) return MI355GS_ELAUNCH;
-  if (cap > 0) {
+  if (f.cap > 0) {
     // deterministic mode: every instance's moments go to a row of their own (binning: det_rows / det_rowidx) and are summed per
     // Gaussian in rectangle order by k_det_gather, which writes every record — instead of meeting in float atomics
     const bool det = fb.knobs.det != 0;
     char* det_scratch = (char*)fb.grad_scratch + gs_grad_gate_offset(P) + 256;
-    uint32_t* rowidx = det ? (uint32_t*)(b + bl.det_rowidx) : nullptr;
-    float* rows = det ? (float*)(b + bl.det_rows) : nullptr;
     if (det) {
       GS_KRANGE("det_prepare");
-      const int rc = gs_launch_det_prepare(stream, P, tl.T, tl.gx, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list),
-                                           (const uint2*)(g + gl.rect), det_scratch, rowidx, rows);
-      GS_CHECK_LAUNCH("det_prepare");
+      const int rc = gs_launch_det_prepare(stream, f, det_scratch);
+      GS_CHECK_LAUNCH_SYNC("det_prepare", stream, debug);
       if (rc != 0) return MI355GS_ELAUNCH;
     }
     {
       ProfScope prof(1, stream);
       GS_KRANGE("composite_bwd");
-      gs_launch_composite_bwd(stream, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list),
-                              (const GsRec*)(g + gl.rec), bg, (const float*)(t + tl.final_T), (const uint32_t*)(t + tl.n_contrib),
-                              dL_dpix, grads, out_color, (const uint4*)(b + bl.unit_tile),
-                              (const float4*)(b + bl.bstate), (const uint32_t*)(t + tl.meta), bl.max_units, bl.may_loop,
-                              (const unsigned long long*)(b + bl.hitmask), bl.max_chunks, (const uint32_t*)(t + tl.qmax),
-                              det ? nullptr : g_prof.work_counters, rowidx, rows);
+      gs_launch_composite_bwd(stream, f, bg, dL_dpix, grads, out_color, det ? nullptr : g_prof.work_counters);
     }
-    GS_CHECK_LAUNCH("composite_bwd");
+    GS_CHECK_LAUNCH_SYNC("composite_bwd", stream, debug);
     if (det) {
       GS_KRANGE("det_gather");
-      gs_launch_det_gather(stream, P, cap, det_scratch, rows, grads);
-      GS_CHECK_LAUNCH("det_gather");
+      gs_launch_det_gather(stream, f, det_scratch, grads);
+      GS_CHECK_LAUNCH_SYNC("det_gather", stream, debug);
     }
   }
   const CamParams cp = make_cam(vw.view, vw.proj, vw.campos, vw.tanfovx, vw.tanfovy, sc.scale_modifier, W, H);
   GS_KRANGE("preprocess_bwd");
-  gs_launch_preprocess_bwd(stream, P, D, sc.M, sc.means3D, sc.shs, sc.shs_rest, sc.scales, sc.rotations, use_shs, use_cov, cp, fb.radii,
-                           (const GsRec*)(g + gl.rec), (const float*)(g + gl.cov3D), (const uint8_t*)(g + gl.clamped), grads, o.means3D,
-                           o.means2D, o.shs, o.shs_rest, o.colors, o.opacities, o.scales, o.rotations, o.cov3D, cx.posed, cx.gate,
-                           cx.pose_only);
-  GS_CHECK_LAUNCH("preprocess_bwd");
+  gs_launch_preprocess_bwd(stream, sc, cp, f, grads, o, cx.posed, cx.gate, cx.pose_only);
+  GS_CHECK_LAUNCH_SYNC("preprocess_bwd", stream, debug);
   return MI355GS_OK;
 }
 
@@ -369,8 +299,7 @@ int mi355gs_raster_depth_forward(void* stream_, int P, int W, int H, int64_t cap
                                  const void* binning, float* out_depth, float* out_alpha) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
-  if (P < 0 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE || !geom || !tiles) return MI355GS_EINVAL;
+  if (P < 0 || !gs_frame_size_ok(W, H) || !geom || !tiles) return MI355GS_EINVAL;
   const uint32_t cap = clamp_capacity(capacity);
   if (cap > 0 && !binning) return MI355GS_EINVAL;
   const size_t map_bytes = (size_t)W * H * sizeof(float);
@@ -380,15 +309,10 @@ int mi355gs_raster_depth_forward(void* stream_, int P, int W, int H, int64_t cap
     return MI355GS_OK;
   }
   if (!out_depth && !out_alpha) return MI355GS_OK;
-  const GeomLayout gl(P);
-  const TilesLayout tl(W, H);
-  const BinningLayout bl(capacity, tl.T, gs_knobs());   // (the list's offset does not depend on the knobs)
-  const char* g = (const char*)geom;
-  const char* t = (const char*)tiles;
-  const char* b = (const char*)binning;
+  // (the list's offset does not depend on the knobs)
+  const GsFrame f({const_cast<void*>(geom), const_cast<void*>(tiles), const_cast<void*>(binning), capacity, nullptr, nullptr, gs_knobs()}, P, W, H);
   GS_KRANGE("depth_fwd");
-  gs_launch_depth_fwd(stream, tl.T, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list), (const GsRec*)(g + gl.rec),
-                      (const float*)(t + tl.final_T), (const uint32_t*)(t + tl.n_contrib), (const uint32_t*)(t + tl.order), out_depth, out_alpha);
+  gs_launch_depth_fwd(stream, f, out_depth, out_alpha);
   GS_CHECK_LAUNCH("depth_fwd");
   return MI355GS_OK;
 }
@@ -401,7 +325,7 @@ int mi355gs_raster_depth_backward(void* stream_, int P, int W, int H, const floa
                                   float* dL_dcov3D, int debug) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  if (P < 0 || W <= 0 || H <= 0 || W > 65535 * GS_TILE || H > 65535 * GS_TILE) return MI355GS_EINVAL;
+  if (P < 0 || !gs_frame_size_ok(W, H)) return MI355GS_EINVAL;
   if (!geom || !tiles || !depth_scratch || !viewmatrix || !projmatrix || !campos) return MI355GS_EINVAL;
   const int use_cov = cov3D_precomp != nullptr;
   if (P > 0 && (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacities)) return MI355GS_EINVAL;
@@ -410,33 +334,28 @@ int mi355gs_raster_depth_backward(void* stream_, int P, int W, int H, const floa
   const uint32_t cap = clamp_capacity(capacity);
   if (cap > 0 && !binning) return MI355GS_EINVAL;
   if (P == 0) return MI355GS_OK;
-  const GeomLayout gl(P);
-  const TilesLayout tl(W, H);
-  const BinningLayout bl(capacity, tl.T, gs_knobs());
+  const GsFrame f({const_cast<void*>(geom), const_cast<void*>(tiles), const_cast<void*>(binning), capacity, const_cast<int32_t*>(radii),
+                   nullptr, gs_knobs()}, P, W, H);
   const DepthScratchLayout dl(P);
-  const char* g = (const char*)geom;
-  const char* t = (const char*)tiles;
-  const char* b = (const char*)binning;
   GsGrad* grads = (GsGrad*)((char*)depth_scratch + dl.grads);
   float* dz = (float*)((char*)depth_scratch + dl.dz);
   if (hipMemsetAsync(depth_scratch, 0, dl.total, stream) != hipSuccess) return MI355GS_ELAUNCH;
-  if (cap > 0 && (dL_ddepth || dL_dalpha)) {
+  if (f.cap > 0 && (dL_ddepth || dL_dalpha)) {
     GS_KRANGE("depth_bwd");
-    gs_launch_depth_bwd(stream, tl.T, tl.gx, W, H, cap, (const uint32_t*)(t + tl.start), (const uint32_t*)(b + bl.list), (const GsRec*)(g + gl.rec),
-                        (const float*)(t + tl.final_T), (const uint32_t*)(t + tl.n_contrib), (const uint32_t*)(t + tl.order), dL_ddepth, dL_dalpha, grads, dz);
-    GS_CHECK_LAUNCH("depth_bwd");
+    gs_launch_depth_bwd(stream, f, dL_ddepth, dL_dalpha, grads, dz);
+    GS_CHECK_LAUNCH_SYNC("depth_bwd", stream, debug);
   }
-  // the moments -> dL/dmean2D, dL/dconic, dL/dopacity -> means, scales, rotations / cov3D: the projection backward in its
-  // precomputed-colour form.  The colour slots of the records are zero, so nothing colour-borne exists: no dL_dcolors is stored.
+  // the moments -> dL/dmean2D, dL/dconic, dL/dopacity -> means, scales, rotations / cov3D: the projection backward over a scene
+  // without colours.  The colour slots of the records are zero, so nothing colour-borne exists: no dL_dcolors is stored.
+  const GsScene sc = {P, 0, 0, means3D, nullptr, nullptr, nullptr, nullptr, scales, rotations, cov3D_precomp, scale_modifier};
+  const GsGradOut o = {dL_dmeans3D, dL_dmeans2D, nullptr, nullptr, nullptr, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D};
   const CamParams cp = make_cam(viewmatrix, projmatrix, campos, tanfovx, tanfovy, scale_modifier, W, H);
   GS_KRANGE("preprocess_bwd");
-  gs_launch_preprocess_bwd(stream, P, 0, 0, means3D, nullptr, nullptr, scales, rotations, 0, use_cov, cp, radii, (const GsRec*)(g + gl.rec),
-                           (const float*)(g + gl.cov3D), (const uint8_t*)(g + gl.clamped), grads, dL_dmeans3D, dL_dmeans2D, nullptr, nullptr,
-                           nullptr, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D, GsPosed(), nullptr, false);
-  GS_CHECK_LAUNCH("preprocess_bwd");
+  gs_launch_preprocess_bwd(stream, sc, cp, f, grads, o, GsPosed(), nullptr, false);
+  GS_CHECK_LAUNCH_SYNC("preprocess_bwd", stream, debug);
   GS_KRANGE("depth_dz");
   gs_launch_depth_dz(stream, P, viewmatrix, dz, dL_dmeans3D);
-  GS_CHECK_LAUNCH("depth_dz");
+  GS_CHECK_LAUNCH_SYNC("depth_dz", stream, debug);
   return MI355GS_OK;
 }
 
@@ -455,13 +374,11 @@ int mi355gs_tune_scale_grad(int mode) {
 int mi355gs_raster_frame_stats(void* stream_, int W, int H, const void* tiles, int64_t* stats) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (W <= 0 || H <= 0 || !tiles || !stats) return MI355GS_EINVAL;
-  const TilesLayout tl(W, H);
-  const char* t = (const char*)tiles;
   if (hipMemsetAsync(stats, 0, 2 * sizeof(int64_t), stream) != hipSuccess) return MI355GS_ELAUNCH;
+  const GsFrame f(const_cast<void*>(tiles), W, H);
   GS_KRANGE("frame_stats");
-  gs_launch_frame_stats(stream, tl.T, tl.gx, W, H, (const uint32_t*)(t + tl.start), (const uint32_t*)(t + tl.n_contrib), stats);
+  gs_launch_frame_stats(stream, f, stats);
   GS_CHECK_LAUNCH("frame_stats");
   return MI355GS_OK;
 }
@@ -516,11 +433,9 @@ int mi355gs_raster_mark_visible(void* stream_, int P, const float* means3D, cons
                                 uint8_t* present) {
   GS_RANGE();
   (void)projmatrix;
-  const int debug = 0;
-  void* stream = stream_;
   if (P < 0 || (P > 0 && (!means3D || !viewmatrix || !present))) return MI355GS_EINVAL;
   GS_KRANGE("mark_visible");
-  gs_launch_mark_visible((hipStream_t)stream, P, means3D, viewmatrix, present);
+  gs_launch_mark_visible((hipStream_t)stream_, P, means3D, viewmatrix, present);
   GS_CHECK_LAUNCH("mark_visible");
   return MI355GS_OK;
 }

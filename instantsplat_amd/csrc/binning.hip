@@ -749,16 +749,16 @@ extern "C" int mi355gs_tune_min_units(int min_units) {
 }
 int gs_min_units() { return g_min_units; }
 
-int gs_launch_scan_tiles(hipStream_t stream, int T, const uint32_t* count, uint32_t* start, int32_t* num_rendered, uint32_t* order,
-                         uint32_t* meta, uint32_t* seg_first, uint32_t* part_first, int min_units) {
+int gs_launch_scan_tiles(hipStream_t stream, const GsFrame& f, int32_t* num_rendered, int min_units) {
+  const int T = f.T;
   // more tiles than threads and the counts fit the workgroup's dynamic LDS: the staged form (see the kernel)
   const size_t stage_bytes = (size_t)((T + SCAN_THREADS - 1) / SCAN_THREADS) * SCAN_THREADS * 4;   // T words, rounded up to whole rounds of the workgroup
   if (T > SCAN_THREADS && stage_bytes <= SCAN_STAGE_MAX_BYTES)
-    hipLaunchKernelGGL(k_scan_tiles<true>, dim3(1), dim3(SCAN_THREADS), stage_bytes, stream, T, count, start, num_rendered, order, meta,
-                       seg_first, part_first, (uint32_t)min_units);
+    hipLaunchKernelGGL(k_scan_tiles<true>, dim3(1), dim3(SCAN_THREADS), stage_bytes, stream, T, f.count, f.start, num_rendered, f.order,
+                       f.meta, f.seg_first, f.part_first, (uint32_t)min_units);
   else
-    hipLaunchKernelGGL(k_scan_tiles<false>, dim3(1), dim3(SCAN_THREADS), 0, stream, T, count, start, num_rendered, order, meta, seg_first,
-                       part_first, (uint32_t)min_units);
+    hipLaunchKernelGGL(k_scan_tiles<false>, dim3(1), dim3(SCAN_THREADS), 0, stream, T, f.count, f.start, num_rendered, f.order, f.meta,
+                       f.seg_first, f.part_first, (uint32_t)min_units);
   return 0;
 }
 
@@ -780,31 +780,31 @@ int gs_launch_scan_rect_areas(hipStream_t stream, int P, const uint2* rects, uin
   return scan_large<true>(stream, P + 1, reinterpret_cast<const uint32_t*>(rects), off, block_sums, total);
 }
 
-int gs_launch_count_tiles(hipStream_t stream, int P, int T, int gx, const uint2* rects, uint32_t* tile_count, uint32_t* entries,
-                          uint32_t* entry_n) {
+int gs_launch_count_tiles(hipStream_t stream, const GsFrame& f) {
+  const int P = f.P, T = f.T;
   if (P <= 0) return 0;
   if (T <= BIN_MAX_LDS_TILES) {
     GsProfScope prof(5, stream);
-    hipLaunchKernelGGL(k_count_tiles_lds, dim3((P + BIN_CHUNK - 1) / BIN_CHUNK), dim3(256), (size_t)T * 4, stream, P, T, gx, rects, tile_count,
-                       entries, entry_n);
+    hipLaunchKernelGGL(k_count_tiles_lds, dim3((P + BIN_CHUNK - 1) / BIN_CHUNK), dim3(256), (size_t)T * 4, stream, P, T, f.gx, f.rects, f.count,
+                       f.bin_entries, f.bin_n);
   }
   else
-    hipLaunchKernelGGL(k_count_tiles_direct, dim3((P + 255) / 256), dim3(256), 0, stream, P, gx, rects, tile_count);
+    hipLaunchKernelGGL(k_count_tiles_direct, dim3((P + 255) / 256), dim3(256), 0, stream, P, f.gx, f.rects, f.count);
   return 0;
 }
 
-int gs_launch_binning(hipStream_t stream, int P, int T, int gx, const float* depths, const uint2* rects, const uint32_t* start,
-                      uint32_t* cursor, uint64_t* keys, uint32_t* list, uint32_t capacity, const uint32_t* order, const uint32_t* entries,
-                      const uint32_t* entry_n) {
-  if (P <= 0 || capacity == 0) return 0;
+int gs_launch_binning(hipStream_t stream, const GsFrame& f) {
+  const int P = f.P, T = f.T;
+  if (P <= 0 || f.cap == 0) return 0;
   if (T <= BIN_MAX_LDS_TILES)
-    hipLaunchKernelGGL(k_scatter_lds, dim3((P + BIN_CHUNK - 1) / BIN_CHUNK), dim3(256), (size_t)T * 4, stream, P, T, gx, depths, rects,
-                       start, cursor, keys, capacity, entries, entry_n);
+    hipLaunchKernelGGL(k_scatter_lds, dim3((P + BIN_CHUNK - 1) / BIN_CHUNK), dim3(256), (size_t)T * 4, stream, P, T, f.gx, f.depths, f.rects,
+                       f.start, f.cursor, f.keys, f.cap, f.bin_entries, f.bin_n);
   else
-    hipLaunchKernelGGL(k_scatter_direct, dim3((P + 255) / 256), dim3(256), 0, stream, P, gx, depths, rects, start, cursor, keys, capacity);
+    hipLaunchKernelGGL(k_scatter_direct, dim3((P + 255) / 256), dim3(256), 0, stream, P, f.gx, f.depths, f.rects, f.start, f.cursor, f.keys,
+                       f.cap);
   {
     GsProfScope prof(4, stream);
-    hipLaunchKernelGGL(k_sort_tiles, dim3(T), dim3(SORT_THREADS), 0, stream, T, start, keys, list, capacity, order);
+    hipLaunchKernelGGL(k_sort_tiles, dim3(T), dim3(SORT_THREADS), 0, stream, T, f.start, f.keys, f.list, f.cap, f.order);
   }
   return 0;
 }

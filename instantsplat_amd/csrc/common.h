@@ -332,18 +332,18 @@ __device__ __forceinline__ int lp_acc_row(int r, int lane) { return (r & 3) + 8 
 
 extern thread_local bool g_krange_open;
 void gs_range_pop();
-#define GS_CHECK_LAUNCH(name)                                                   \
-  do {                                                                          \
-    if (g_krange_open) { g_krange_open = false; gs_range_pop(); }               \
-    hipError_t e_ = hipGetLastError();                                          \
-    if (e_ == hipSuccess && debug) e_ = hipStreamSynchronize((hipStream_t)stream); \
-    if (e_ != hipSuccess) {                                                     \
-      gs_log_error(name, hipGetErrorString(e_));                                \
-      return MI355GS_ELAUNCH;                                                   \
-    }                                                                           \
-  } while (0)
-
 void gs_log_error(const char* where, const char* what);
+// Behind every launch: closes the launch's range (GS_KRANGE) and reports a launch error.  GS_CHECK_LAUNCH_SYNC is the form of
+// the operators that have a `debug` argument (mi355gs_raster_*, mi355gs_posed_*): with debug != 0 it waits for the kernel too.
+inline bool gs_launch_failed(const char* name, hipStream_t stream = nullptr, int debug = 0) {
+  if (g_krange_open) { g_krange_open = false; gs_range_pop(); }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && debug) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) gs_log_error(name, hipGetErrorString(e));
+  return e != hipSuccess;
+}
+#define GS_CHECK_LAUNCH(name) do { if (gs_launch_failed(name)) return MI355GS_ELAUNCH; } while (0)
+#define GS_CHECK_LAUNCH_SYNC(name, stream, debug) do { if (gs_launch_failed(name, stream, debug)) return MI355GS_ELAUNCH; } while (0)
 
 // roctx range around an entry point's launches (mi355gs_profile_ranges, api.hip): one predictable branch when off
 extern bool g_ranges_on;
@@ -425,11 +425,92 @@ static inline size_t gs_binning_bytes(int64_t n, int W, int H, const GsKnobs& k,
   const BinningLayout bl(n, TilesLayout(W, H).T, k);
   return train ? bl.total : bl.unit_tile;   // render-only: keys + list, everything in front of the backward's tables
 }
+// W x H is a frame the kernels can take: the tile grid's dimensions are launch-grid dimensions
+static inline bool gs_frame_size_ok(int W, int H) { return W > 0 && H > 0 && W <= 65535 * GS_TILE && H <= 65535 * GS_TILE; }
+static inline uint32_t clamp_capacity(int64_t c) { return c <= 0 ? 0u : (c > 0x7fffffffLL ? 0x7fffffffu : (uint32_t)c); }
+
+// Typed pointers into one frame's scratch buffers.  The layouts above say what a buffer contains; this is the one place that
+// gives each field its type.  Built once per call from the buffers and (P, W, H > 0); a null buffer gives null pointers.
+struct GsFrame {
+  int P, W, H, T, gx;
+  uint32_t cap;                        // instances `binning` holds, as the kernels take it
+  // geom
+  GsRec* recs; float* cov3D; uint2* rects; uint8_t* clamped; float* depths; uint32_t *bin_entries, *bin_n;
+  // tiles
+  uint32_t *count, *cursor, *start; float* final_T; uint32_t *n_contrib, *order, *seg_first, *part_first, *meta, *qmax;
+  int n_counters;                      // count + cursor words: what a prologue clears
+  // binning; the deterministic mode's rows are null outside it
+  uint64_t* keys; uint32_t* list; uint4* unit_tile; float4* bstate; unsigned long long* hitmask; float* det_rows; uint32_t* det_rowidx;
+  uint32_t max_units, max_chunks; bool may_loop;
+  int32_t* radii; void* grad_scratch; GsKnobs knobs;
+
+  GsFrame(const GsFrameBufs& fb, int P_, int W_, int H_)
+      : P(P_), W(W_), H(H_), cap(clamp_capacity(fb.capacity)), radii(fb.radii), grad_scratch(fb.grad_scratch), knobs(fb.knobs) {
+    const GeomLayout gl(P);
+    const TilesLayout tl(W, H);
+    const BinningLayout bl(fb.capacity, tl.T, fb.knobs);
+    T = tl.T; gx = tl.gx;
+    recs = at<GsRec>(fb.geom, gl.rec); cov3D = at<float>(fb.geom, gl.cov3D); rects = at<uint2>(fb.geom, gl.rect);
+    clamped = at<uint8_t>(fb.geom, gl.clamped); depths = at<float>(fb.geom, gl.depth);
+    bin_entries = at<uint32_t>(fb.geom, gl.bin_entries); bin_n = at<uint32_t>(fb.geom, gl.bin_n);
+    count = at<uint32_t>(fb.tiles, tl.count); cursor = at<uint32_t>(fb.tiles, tl.cursor); start = at<uint32_t>(fb.tiles, tl.start);
+    final_T = at<float>(fb.tiles, tl.final_T); n_contrib = at<uint32_t>(fb.tiles, tl.n_contrib); order = at<uint32_t>(fb.tiles, tl.order);
+    seg_first = at<uint32_t>(fb.tiles, tl.seg_first); part_first = at<uint32_t>(fb.tiles, tl.part_first);
+    meta = at<uint32_t>(fb.tiles, tl.meta); qmax = at<uint32_t>(fb.tiles, tl.qmax);
+    n_counters = (int)((tl.start - tl.count) / 4);
+    keys = at<uint64_t>(fb.binning, bl.keys); list = at<uint32_t>(fb.binning, bl.list);   // (the render-only buffer ends here)
+    unit_tile = at<uint4>(fb.binning, bl.unit_tile); bstate = at<float4>(fb.binning, bl.bstate);
+    hitmask = at<unsigned long long>(fb.binning, bl.hitmask);
+    det_rows = at<float>(knobs.det ? fb.binning : nullptr, bl.det_rows);
+    det_rowidx = at<uint32_t>(knobs.det ? fb.binning : nullptr, bl.det_rowidx);
+    max_units = bl.max_units; max_chunks = bl.max_chunks; may_loop = bl.may_loop;
+  }
+  // a view of `tiles` alone (frame statistics, the frame's count): only the tiles fields, T and gx mean anything in it
+  GsFrame(void* tiles, int W_, int H_) : GsFrame({nullptr, tiles, nullptr, 0, nullptr, nullptr, GsKnobs{GS_MIN_UNITS, 0}}, 0, W_, H_) {}
+
+ private:
+  template <class T_> static T_* at(void* base, size_t off) { return base ? (T_*)((char*)base + off) : nullptr; }
+};
 // the frame's true instance count: tile_start[T], written by the tile scan
 static inline const uint32_t* gs_frame_count(const void* tiles, int W, int H) {
-  const TilesLayout tl(W, H);
-  return (const uint32_t*)((const char*)tiles + tl.start) + tl.T;
+  const GsFrame f(const_cast<void*>(tiles), W, H);
+  return f.start + f.T;
 }
+
+// ---- The launchers, each implemented next to its kernels.  A launcher over a frame takes the view and what is not in it.
+// preprocess.hip: projection forward / backward (`grads`: the composite backward's moment records), reference markVisible
+int gs_launch_preprocess_fwd(hipStream_t stream, const GsScene& sc, const CamParams& cp, const GsFrame& f, uint8_t* visible,
+                             const GsPosed& posed_args, const GsPrologue& pro);
+int gs_launch_preprocess_bwd(hipStream_t stream, const GsScene& sc, const CamParams& cp, const GsFrame& f, const GsGrad* grads,
+                             const GsGradOut& o, const GsPosed& posed_args, float* gate_flags, bool pose_only);
+int gs_launch_mark_visible(hipStream_t stream, int P, const float* means3D, const float* view, uint8_t* present);
+// binning.hip: per-tile counts; tile scan (writes the frame's count to *num_rendered too); scatter + per-tile sort; and the
+// plain exclusive scans: n counters into out[0..n], the rectangles' tile counts into off[0..P]
+int gs_launch_count_tiles(hipStream_t stream, const GsFrame& f);
+int gs_launch_scan_tiles(hipStream_t stream, const GsFrame& f, int32_t* num_rendered, int min_units);
+int gs_launch_binning(hipStream_t stream, const GsFrame& f);
+int gs_launch_scan_large(hipStream_t stream, int n, const uint32_t* in, uint32_t* out, uint32_t* block_sums, int32_t* total);
+int gs_launch_scan_rect_areas(hipStream_t stream, int P, const uint2* rects, uint32_t* off, uint32_t* block_sums, int32_t* total);
+// composite.hip: colour forward (train: leaves the backward's tables; `counters`: work counters or null) and backward (into the
+// deterministic mode's rows when the frame has them, det_prepare / det_gather around it), frame statistics, depth and alpha maps
+int gs_launch_composite_fwd(hipStream_t stream, const GsFrame& f, const float* bg, float* out_color, unsigned long long* counters,
+                            bool train);
+int gs_launch_composite_bwd(hipStream_t stream, const GsFrame& f, const float* bg, const float* dL_dpix, GsGrad* grads,
+                            const float* out_color, unsigned long long* counters);
+int gs_launch_det_prepare(hipStream_t stream, const GsFrame& f, char* det_scratch);
+int gs_launch_det_gather(hipStream_t stream, const GsFrame& f, const char* det_scratch, GsGrad* grads);
+int gs_launch_frame_stats(hipStream_t stream, const GsFrame& f, int64_t* stats);
+int gs_launch_depth_fwd(hipStream_t stream, const GsFrame& f, float* out_depth, float* out_alpha);
+int gs_launch_depth_bwd(hipStream_t stream, const GsFrame& f, const float* dL_ddepth, const float* dL_dalpha, GsGrad* grads, float* dz);
+int gs_launch_depth_dz(hipStream_t stream, int P, const float* view, const float* dz, float* dL_dmeans3D);
+// pose.hip, ssim.hip: what the one-call train step launches beside the frame
+int gs_launch_pose_finish_partials(hipStream_t stream, const float* pose, const float* partial, int nrows, float* d_pose,
+                                   float* pose_gate, const float* loss_partial, int loss_nblocks, double loss_inv_n,
+                                   float lambda_dssim, float* loss, int table_rows, int table_row);
+int gs_loss_fused(hipStream_t stream, int C, int H, int W, const float* img1, const float* img2, float lambda_dssim, float* dL_dimg1,
+                  void* scratch);
+int gs_loss_fused_nblocks(int C, int H, int W);
+
 // projection + tile count + tile scan; stage 2 (train: leaves the backward's tables; else render-only); backward
 int gs_frame_project(hipStream_t stream, const GsScene& sc, const GsView& vw, const GsFrameBufs& fb, const GsFrameCtx& cx,
                      int32_t* num_rendered, uint8_t* visible, int debug);
@@ -467,8 +548,7 @@ struct GsFrozenScene {
   // create-time checks and the scene's fields; false: refuse the handle
   bool init(int P_, int M_, int W_, int H_, int64_t capacity_, const float* xyz_, const float* f_dc_, const float* f_rest_,
             const float* opacity_, const float* scaling_, const float* rotation_, const void* workspace) {
-    if (P_ <= 0 || M_ < 1 || M_ > 16 || W_ <= 0 || H_ <= 0 || W_ > 65535 * GS_TILE || H_ > 65535 * GS_TILE || capacity_ <= 0 || !workspace)
-      return false;
+    if (P_ <= 0 || M_ < 1 || M_ > 16 || !gs_frame_size_ok(W_, H_) || capacity_ <= 0 || !workspace) return false;
     if (!xyz_ || !f_dc_ || (M_ > 1 && !f_rest_) || !opacity_ || !scaling_ || !rotation_) return false;
     P = P_; M = M_; W = W_; H = H_; capacity = capacity_;
     xyz = xyz_; f_dc = f_dc_; f_rest = M_ > 1 ? f_rest_ : nullptr; opacity = opacity_; scaling = scaling_; rotation = rotation_;

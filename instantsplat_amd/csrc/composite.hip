@@ -670,35 +670,29 @@ __global__ __launch_bounds__(256) void k_frame_stats(int T, int gx, int W, int H
 
 }  // namespace
 
-int gs_launch_scan_rect_areas(hipStream_t, int, const uint2*, uint32_t*, uint32_t*, int32_t*);
 // deterministic mode, in front of the composite backward: row offsets (a scan over the rectangles' tile counts) -> the row of
 // every list position; the rows cleared.  scratch: DetScratchLayout(P) (uint32 words behind the gradient scratch's gate flags).
-int gs_launch_det_prepare(hipStream_t stream, int P, int T, int gx, uint32_t capacity, const uint32_t* tile_start, const uint32_t* list,
-                          const uint2* rects, char* det_scratch, uint32_t* rowidx, float* rows) {
-  const DetScratchLayout dl(P);
+int gs_launch_det_prepare(hipStream_t stream, const GsFrame& f, char* det_scratch) {
+  const DetScratchLayout dl(f.P);
   uint32_t* off = (uint32_t*)(det_scratch + dl.off);
-  gs_launch_scan_rect_areas(stream, P, rects, off, (uint32_t*)(det_scratch + dl.block_sums), (int32_t*)(off + P + 1));
-  hipLaunchKernelGGL(k_det_rowidx, dim3(T), dim3(256), 0, stream, gx, capacity, tile_start, list, rects, off, rowidx);
-  if (hipMemsetAsync(rows, 0, (size_t)capacity * sizeof(GsGrad), stream) != hipSuccess) return -1;
+  gs_launch_scan_rect_areas(stream, f.P, f.rects, off, (uint32_t*)(det_scratch + dl.block_sums), (int32_t*)(off + f.P + 1));
+  hipLaunchKernelGGL(k_det_rowidx, dim3(f.T), dim3(256), 0, stream, f.gx, f.cap, f.start, f.list, f.rects, off, f.det_rowidx);
+  if (hipMemsetAsync(f.det_rows, 0, (size_t)f.cap * sizeof(GsGrad), stream) != hipSuccess) return -1;
   return 0;
 }
-int gs_launch_det_gather(hipStream_t stream, int P, uint32_t capacity, const char* det_scratch, const float* rows, GsGrad* grads) {
-  const DetScratchLayout dl(P);
-  hipLaunchKernelGGL(k_det_gather, dim3((P + 15) / 16), dim3(192), 0, stream, P, capacity, (const uint32_t*)(det_scratch + dl.off), rows, grads);
-  return 0;
-}
-
-int gs_launch_frame_stats(hipStream_t stream, int T, int gx, int W, int H, const uint32_t* tile_start, const uint32_t* n_contrib,
-                          int64_t* stats) {
-  hipLaunchKernelGGL(k_frame_stats, dim3(T), dim3(256), 0, stream, T, gx, W, H, tile_start, n_contrib, stats);
+int gs_launch_det_gather(hipStream_t stream, const GsFrame& f, const char* det_scratch, GsGrad* grads) {
+  const DetScratchLayout dl(f.P);
+  hipLaunchKernelGGL(k_det_gather, dim3((f.P + 15) / 16), dim3(192), 0, stream, f.P, f.cap, (const uint32_t*)(det_scratch + dl.off), f.det_rows, grads);
   return 0;
 }
 
-int gs_launch_composite_fwd(hipStream_t stream, int T, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start,
-                            const uint32_t* list, const GsRec* recs, const float* bg, float* out_color, float* final_T,
-                            uint32_t* n_contrib, const uint32_t* order, const uint32_t* seg_first, const uint32_t* part_first,
-                            uint4* unit_tile, float4* bstate, uint32_t max_units, const uint32_t* meta, unsigned long long* hitmask,
-                            uint32_t max_chunks, uint32_t* qmax, unsigned long long* counters, bool train) {
+int gs_launch_frame_stats(hipStream_t stream, const GsFrame& f, int64_t* stats) {
+  hipLaunchKernelGGL(k_frame_stats, dim3(f.T), dim3(256), 0, stream, f.T, f.gx, f.W, f.H, f.start, f.n_contrib, stats);
+  return 0;
+}
+
+int gs_launch_composite_fwd(hipStream_t stream, const GsFrame& f, const float* bg, float* out_color, unsigned long long* counters,
+                            bool train) {
   // equal-weight workgroups of 4 (2) tiles while the whole frame is one resident round of at most one (two) workgroups per CU
   // (the count belongs to the device the launch goes to — the process's current one — not to whichever device was current
   // the first time: a process that drives two different GPUs gets each one's own; a device attribute read is host-only and cheap,
@@ -712,10 +706,12 @@ int gs_launch_composite_fwd(hipStream_t stream, int T, int gx, int W, int H, uin
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     cus_of[dev] = cus = n;
   }
-  const int per_wg = T <= 4 * cus ? 4 : (T <= 4 * cus * 2 ? 2 : 1);
+  const int T = f.T, per_wg = T <= 4 * cus ? 4 : (T <= 4 * cus * 2 ? 2 : 1);
+  // (render-only leaves no work units, boundary records or hit masks: its buffer ends behind the lists)
 #define GS_FWD(N, CNT, TRN)                                                                                                         \
-  hipLaunchKernelGGL((k_composite_fwd<N, CNT, TRN>), dim3((T + N - 1) / N), dim3(256 * N), 0, stream, T, gx, W, H, capacity, tile_start, list, recs, bg, \
-                     out_color, final_T, n_contrib, order, seg_first, part_first, unit_tile, bstate, max_units, meta, hitmask, max_chunks, qmax, counters)
+  hipLaunchKernelGGL((k_composite_fwd<N, CNT, TRN>), dim3((T + N - 1) / N), dim3(256 * N), 0, stream, T, f.gx, f.W, f.H, f.cap, f.start, f.list, f.recs, bg, \
+                     out_color, f.final_T, f.n_contrib, f.order, f.seg_first, f.part_first, train ? f.unit_tile : nullptr,               \
+                     train ? f.bstate : nullptr, f.max_units, f.meta, train ? f.hitmask : nullptr, f.max_chunks, f.qmax, counters)
   if (!train) { if (per_wg == 4) GS_FWD(4, false, false); else if (per_wg == 2) GS_FWD(2, false, false); else GS_FWD(1, false, false); }
   else if (counters) { if (per_wg == 4) GS_FWD(4, true, true); else if (per_wg == 2) GS_FWD(2, true, true); else GS_FWD(1, true, true); }
   else { if (per_wg == 4) GS_FWD(4, false, true); else if (per_wg == 2) GS_FWD(2, false, true); else GS_FWD(1, false, true); }
@@ -725,22 +721,19 @@ int gs_launch_composite_fwd(hipStream_t stream, int T, int gx, int W, int H, uin
 
 // one wave per backward unit, one unit per workgroup; the grid covers every unit the buffers can hold, waves past the
 // frame's count exit
-int gs_launch_composite_bwd(hipStream_t stream, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start,
-                            const uint32_t* list, const GsRec* recs, const float* bg, const float* final_T,
-                            const uint32_t* n_contrib, const float* dL_dpix, GsGrad* grads, const float* out_color,
-                            const uint4* unit_tile, const float4* bstate, const uint32_t* meta,
-                            uint32_t max_units, bool may_loop, const unsigned long long* hitmask, uint32_t max_chunks,
-                            const uint32_t* qmax, unsigned long long* counters, const uint32_t* det_rowidx, float* det_rows) {
+int gs_launch_composite_bwd(hipStream_t stream, const GsFrame& f, const float* bg, const float* dL_dpix, GsGrad* grads,
+                            const float* out_color, unsigned long long* counters) {
   // whole blocks of launch positions (see the index transposition in the kernel)
   const uint32_t blk = 8u * BW_XCD_RUN;
-  const dim3 grid((max_units + blk - 1u) / blk * blk);
+  const dim3 grid((f.max_units + blk - 1u) / blk * blk);
   // may_loop == false: a frame that fits this capacity has one-chunk units (count <= capacity), so the lean instantiation is safe
 #define GS_BWD(CH, CNT, DT)                                                                                                           \
-  hipLaunchKernelGGL((k_composite_bwd<CH, CNT, DT>), grid, dim3(64), 0, stream, gx, W, H, capacity, tile_start, list, recs, bg, final_T,  \
-                     n_contrib, dL_dpix, grads, out_color, unit_tile, bstate, meta, max_units, counters, hitmask, max_chunks, qmax, det_rowidx, det_rows)
-  if (det_rows) { if (!may_loop) GS_BWD(1, false, true); else GS_BWD(0, false, true); }
-  else if (counters) { if (!may_loop) GS_BWD(1, true, false); else GS_BWD(0, true, false); }
-  else { if (!may_loop) GS_BWD(1, false, false); else GS_BWD(0, false, false); }
+  hipLaunchKernelGGL((k_composite_bwd<CH, CNT, DT>), grid, dim3(64), 0, stream, f.gx, f.W, f.H, f.cap, f.start, f.list, f.recs, bg, f.final_T,  \
+                     f.n_contrib, dL_dpix, grads, out_color, f.unit_tile, f.bstate, f.meta, f.max_units, counters, f.hitmask, f.max_chunks, \
+                     f.qmax, f.det_rowidx, f.det_rows)
+  if (f.det_rows) { if (!f.may_loop) GS_BWD(1, false, true); else GS_BWD(0, false, true); }
+  else if (counters) { if (!f.may_loop) GS_BWD(1, true, false); else GS_BWD(0, true, false); }
+  else { if (!f.may_loop) GS_BWD(1, false, false); else GS_BWD(0, false, false); }
 #undef GS_BWD
   return 0;
 }
@@ -920,16 +913,14 @@ __global__ __launch_bounds__(256) void k_depth_dz(int P, const float* __restrict
 
 }  // namespace
 
-int gs_launch_depth_fwd(hipStream_t stream, int T, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start, const uint32_t* list,
-                        const GsRec* recs, const float* final_T, const uint32_t* n_contrib, const uint32_t* order, float* out_depth, float* out_alpha) {
-  hipLaunchKernelGGL(k_depth_fwd, dim3(T), dim3(256), 0, stream, gx, W, H, capacity, tile_start, list, recs, final_T, n_contrib, order, out_depth, out_alpha);
+int gs_launch_depth_fwd(hipStream_t stream, const GsFrame& f, float* out_depth, float* out_alpha) {
+  hipLaunchKernelGGL(k_depth_fwd, dim3(f.T), dim3(256), 0, stream, f.gx, f.W, f.H, f.cap, f.start, f.list, f.recs, f.final_T, f.n_contrib, f.order,
+                     out_depth, out_alpha);
   return 0;
 }
-int gs_launch_depth_bwd(hipStream_t stream, int T, int gx, int W, int H, uint32_t capacity, const uint32_t* tile_start, const uint32_t* list,
-                        const GsRec* recs, const float* final_T, const uint32_t* n_contrib, const uint32_t* order, const float* dL_ddepth,
-                        const float* dL_dalpha, GsGrad* grads, float* dz) {
-  hipLaunchKernelGGL(k_depth_bwd, dim3(T), dim3(256), 0, stream, gx, W, H, capacity, tile_start, list, recs, final_T, n_contrib, order, dL_ddepth,
-                     dL_dalpha, grads, dz);
+int gs_launch_depth_bwd(hipStream_t stream, const GsFrame& f, const float* dL_ddepth, const float* dL_dalpha, GsGrad* grads, float* dz) {
+  hipLaunchKernelGGL(k_depth_bwd, dim3(f.T), dim3(256), 0, stream, f.gx, f.W, f.H, f.cap, f.start, f.list, f.recs, f.final_T, f.n_contrib, f.order,
+                     dL_ddepth, dL_dalpha, grads, dz);
   return 0;
 }
 int gs_launch_depth_dz(hipStream_t stream, int P, const float* view, const float* dz, float* dL_dmeans3D) {

@@ -387,7 +387,6 @@ int mi355gs_density_stats(void* stream_, int P, const float* grad, int grad_stri
                           float* grad_accum, float* denom, float* max_radii) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (P <= 0 || !grad || grad_stride < 2 || (!filter && !radii) || !grad_accum || !denom) return MI355GS_EINVAL;
   GS_KRANGE("density_stats");
   hipLaunchKernelGGL(k_density_stats, dim3((P + 255) / 256), dim3(256), 0, stream, P, grad, grad_stride, filter, radii, grad_accum, denom, max_radii);
@@ -406,7 +405,6 @@ int mi355gs_density_plan(void* stream_, int P, int N, int flags, const float* gr
                          float child_div, uint32_t* code, void* scratch, int32_t* totals_host) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const int all = MI355GS_DENSITY_CLONE | MI355GS_DENSITY_SPLIT | MI355GS_DENSITY_PRUNE | MI355GS_DENSITY_SCREEN;
   if (!density_size_ok(P, N) || (flags & ~all) || !(flags & (all & ~MI355GS_DENSITY_SCREEN)) || !scaling || !opacity || !code || !scratch)
     return MI355GS_EINVAL;
@@ -435,7 +433,6 @@ int mi355gs_density_apply(void* stream_, int P, int N, int flags, int rest_width
                           void* const* out, int64_t out_rows) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!density_size_ok(P, N) || rest_width < 0 || rest_width > 3 * 255 || !code || !scratch || !in || !out) return MI355GS_EINVAL;
   if (out_rows < 0 || out_rows > 0x7fffffffLL || noise_rows < 0 || n_selected < 0 || n_selected > P) return MI355GS_EINVAL;
   if ((flags & MI355GS_DENSITY_SPLIT) && n_selected > 0 && (!noise || noise_rows < (int64_t)N * n_selected || !(child_div > 0.0f)))
@@ -466,7 +463,6 @@ int mi355gs_density_apply(void* stream_, int P, int N, int flags, int rest_width
 int mi355gs_reset_opacity(void* stream_, int P, float* opacity, float* exp_avg, float* exp_avg_sq) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (P <= 0 || !opacity) return MI355GS_EINVAL;
   GS_KRANGE("reset_opacity");
   hipLaunchKernelGGL(k_reset_opacity, dim3((P + 255) / 256), dim3(256), 0, stream, P, opacity, exp_avg, exp_avg_sq);

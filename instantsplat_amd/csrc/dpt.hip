@@ -248,7 +248,6 @@ int dp_conv_nt(int Cout) { return Cout % 128 == 0 ? 4 : Cout % 64 == 0 ? 2 : 1; 
 
 int dp_conv(hipStream_t stream, int E, int Hi, int Wi, int stride, bool relu_in, int Cin, int Cout, const float* in, const float* wt, bool has_bias,
             const float* r1, const float* r2, float* out) {
-  const int debug = 0;
   const int Ho = (Hi + stride - 1) / stride, Wo = (Wi + stride - 1) / stride;
   const MmConv g = {E * Ho * Wo, Hi, Wi, Ho, Wo, Cin, Cout, stride, relu_in ? 1 : 0};
   const float* bias = has_bias ? wt + (size_t)9 * Cin * Cout : nullptr;
@@ -265,7 +264,6 @@ int dp_conv(hipStream_t stream, int E, int Hi, int Wi, int stride, bool relu_in,
 }
 
 int dp_up2(hipStream_t stream, int E, int hi, int wi, int ho, int wo, int C, const float* in, float* out) {
-  const int debug = 0;
   const long long total4 = (long long)E * ho * wo * (C / 4);
   const float sy = hi > 1 ? (float)(hi - 1) / (float)(2 * hi - 1) : 0.f, sx = wi > 1 ? (float)(wi - 1) / (float)(2 * wi - 1) : 0.f;
   GS_KRANGE("dpt_up2");
@@ -339,7 +337,6 @@ int mi355gs_dpt_head(void* stream_, const mi355gs_dpt_config* cfg, const float* 
                      void* scratch, float* pts3d, float* conf, float* raw4) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const DpPlan p(cfg, Ht, Wt, E);
   if (!p.ok || !weights || !hooks || !scratch || !pts3d || !conf) return MI355GS_EINVAL;
   if (!dp_aligned(weights, scratch, raw4, nullptr) || (((uintptr_t)pts3d | (uintptr_t)conf) & 3)) return MI355GS_EINVAL;
@@ -420,7 +417,6 @@ int mi355gs_local_features(void* stream_, const mi355gs_dpt_config* cfg, const f
                            const float* hook3, void* scratch, float* desc, float* desc_conf) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const DpMlp m(cfg, Ht, Wt, E);
   if (!m.ok || !weights || !hook0 || !hook3 || !scratch || !desc || (m.two && !desc_conf)) return MI355GS_EINVAL;
   if (!dp_aligned(weights, hook0, hook3, scratch) || (((uintptr_t)desc | (uintptr_t)desc_conf) & 3)) return MI355GS_EINVAL;

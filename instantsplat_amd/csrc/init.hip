@@ -268,7 +268,6 @@ int mi355gs_pointmap_stats(void* stream_, int V, int H, int W, const float* dept
                            void* scratch, double* stats) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!init_size_ok(V, H, W) || !depthmaps || !confidences || !overlap || !scratch || !stats) return MI355GS_EINVAL;
   const int chunks = stats_chunks(H, W);
   GS_KRANGE("pointmap_stats");
@@ -285,7 +284,6 @@ int mi355gs_covis_masks(void* stream_, int V, int H, int W, const int32_t* order
                         const float* intrinsics, const float* w2c, const double* stats, float depth_threshold, uint8_t* overlap) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!init_size_ok(V, H, W) || !order || !pointmaps || !depthmaps || !intrinsics || !w2c || !stats || !overlap) return MI355GS_EINVAL;
   ViewOrder vo;
   bool seen[MAX_VIEWS] = {false};
@@ -314,7 +312,6 @@ int mi355gs_compact_pointmaps(void* stream_, int64_t n, const uint8_t* overlap, 
                               int32_t* count_dev, int32_t* count_host) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!compact_size_ok(n) || !pointmaps || !images || !confidences || !scratch || !out_points || !out_rgb8 || !out_confidence || !count_dev)
     return MI355GS_EINVAL;
   const int nblocks = compact_blocks(n);

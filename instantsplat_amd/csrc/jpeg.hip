@@ -416,7 +416,6 @@ int mi355gs_jpeg_rgb8(void* stream_, int N, int H, int W, int subsampling, const
                       uint8_t* out, size_t out_bytes, int64_t* offsets) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const JpgLayout jl(N, H, W, subsampling);
   if (!jl.ok || !qtables || !frames || !scratch || !out || !offsets || ((uintptr_t)scratch & 15) || ((uintptr_t)offsets & 7)) return MI355GS_EINVAL;
   JpgQuant qt;

@@ -12,8 +12,6 @@
 // whose search has not terminated after KNN_MAX_RING shells, e.g. far outliers, and for tiny clouds).
 #include "common.h"
 
-int gs_launch_scan_large(hipStream_t, int, const uint32_t*, uint32_t*, uint32_t*, int32_t*);
-
 namespace {
 
 constexpr int KNN_MAX_RING = 6;
@@ -189,7 +187,6 @@ size_t mi355gs_knn_scratch_bytes(int N) { return KnnLayout(N).total + 256; }
 int mi355gs_knn_dist2(void* stream_, int N, const float* points, float* mean_dist2, void* scratch) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (N < 0 || (N > 0 && (!points || !mean_dist2 || !scratch))) return MI355GS_EINVAL;
   if (N == 0) return MI355GS_OK;
   const KnnLayout L(N);

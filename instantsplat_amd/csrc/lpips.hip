@@ -215,7 +215,6 @@ struct LpPlan {
 };
 
 int lp_conv(hipStream_t stream, int P, int H, int W, int Cin, int Cout, const float* in, const float* wt, const float* bias, float* out) {
-  const int debug = 0;
   const int nt = Cout % 128 == 0 ? 4 : Cout % 96 == 0 ? 3 : Cout % 64 == 0 ? 2 : 1;
   const dim3 grid((unsigned)((P + MM_BM - 1) / MM_BM), (unsigned)(Cout / (32 * nt)));
   GS_KRANGE("lpips_conv");
@@ -242,7 +241,6 @@ int mi355gs_lpips_vgg_rgb8(void* stream_, int N, int H, int W, const uint8_t* a,
                            const float* weights, void* scratch, float* lpips, float* taps) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const LpPlan plan(N, H, W, channels);
   if (!plan.ok || !a || !b || !weights || !scratch || !lpips) return MI355GS_EINVAL;
   if ((((uintptr_t)weights | (uintptr_t)scratch) & 15) != 0) return MI355GS_EINVAL;

@@ -154,7 +154,6 @@ __global__ __launch_bounds__(MM_T) void k_vit_gemm(int M, int K, int N, const fl
 // of 64 runs 128 x 32 tiles.
 template <bool THIN32 = false>
 int vt_gemm(hipStream_t stream, int epi, int M, int K, int N, const float* A, const float* wt, const float* resid, float* out) {
-  const int debug = 0;
   const float* bias = wt + (size_t)K * N;
   const unsigned mt = (unsigned)((M + MM_BM - 1) / MM_BM);
   const bool wide = N % 128 == 0 && (long long)mt * (N / 128) >= 256;

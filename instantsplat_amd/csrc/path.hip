@@ -61,7 +61,6 @@ __global__ __launch_bounds__(256) void k_rgb8_from_planar(int npix, const float*
 bool rgb8_size_ok(int W, int H) { return W > 0 && H > 0 && (long long)W * H <= 0x7fffffffLL - 256 * RGB8_VEC; }
 
 int launch_rgb8(hipStream_t stream, int W, int H, const float* img, uint8_t* out, const uint32_t* count_src, int32_t* count_dst) {
-  const int debug = 0;
   const int npix = W * H;
   const int per_block = 256 * RGB8_VEC;
   GS_KRANGE("rgb8_from_planar");

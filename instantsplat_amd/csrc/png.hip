@@ -475,7 +475,6 @@ int mi355gs_png_rgb8(void* stream_, int N, int H, int W, int rows_per_block, con
                      int64_t* offsets) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const PngLayout pl(N, H, W, rows_per_block);
   if (!pl.ok || !frames || !scratch || !out || !offsets || ((uintptr_t)scratch & 15) || ((uintptr_t)offsets & 7)) return MI355GS_EINVAL;
   uint8_t* slots = (uint8_t*)scratch + pl.slots;

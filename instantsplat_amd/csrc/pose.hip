@@ -170,7 +170,6 @@ int mi355gs_pose_forward(void* stream_, int P, const float* xyz, const float* ro
                          float* opac) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (P < 0 || !pose) return MI355GS_EINVAL;
   if (P == 0) return MI355GS_OK;
   if (!xyz || !rot || !scaling || !opacity_logit || !means_cam || !rot_cam || !scales || !opac) return MI355GS_EINVAL;
@@ -188,7 +187,6 @@ int mi355gs_pose_backward(void* stream_, int P, const float* xyz, const float* r
                           float* d_pose, float* scratch16) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (P < 0 || !pose || !d_pose || !scratch16) return MI355GS_EINVAL;
   if (hipMemsetAsync(scratch16, 0, 32 * sizeof(float), stream) != hipSuccess) return MI355GS_ELAUNCH;
   if (P > 0) {

@@ -554,30 +554,26 @@ __global__ __launch_bounds__(256) void k_mark_visible(int P, const float* __rest
 }  // namespace
 
 // ---- host-side launchers (called from api.hip)
-int gs_launch_preprocess_fwd(hipStream_t stream, int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest,
-                             const float* colors_precomp, const float* opacities, const float* scales,
-                             const float* rotations, const float* cov3D_precomp, const CamParams& cp, int32_t* radii,
-                             GsRec* recs, float* cov3Ds, uint2* rects, uint8_t* clamped, float* depths, uint8_t* visible,
+int gs_launch_preprocess_fwd(hipStream_t stream, const GsScene& sc, const CamParams& cp, const GsFrame& f, uint8_t* visible,
                              const GsPosed& posed_args, const GsPrologue& pro) {
+  const int P = sc.P;
   if (P <= 0) return 0;
   const bool posed = posed_args.pose != nullptr;
   const GsPosed pa = posed ? posed_args : GsPosed();
 #define GS_FWD(POSED, DEG)                                                                                                              \
-  hipLaunchKernelGGL((k_preprocess_fwd<POSED, DEG>), dim3((P + 255) / 256), dim3(256), 0, stream, P, M, means3D, shs, shs_rest,         \
-                     colors_precomp, opacities, scales, rotations, cov3D_precomp, cp, radii, recs, cov3Ds, rects, clamped, depths, visible, pa, pro)
-  const int deg = shs ? D : 0;  // one instantiation per active SH degree: coefficient arrays stay in registers
+  hipLaunchKernelGGL((k_preprocess_fwd<POSED, DEG>), dim3((P + 255) / 256), dim3(256), 0, stream, P, sc.M, sc.means3D, sc.shs,          \
+                     sc.shs_rest, sc.colors_precomp, sc.opacities, sc.scales, sc.rotations, sc.cov3D_precomp, cp, f.radii, f.recs,      \
+                     f.cov3D, f.rects, f.clamped, f.depths, visible, pa, pro)
+  const int deg = sc.shs ? sc.D : 0;  // one instantiation per active SH degree: coefficient arrays stay in registers
   if (posed) { if (deg == 0) GS_FWD(true, 0); else if (deg == 1) GS_FWD(true, 1); else if (deg == 2) GS_FWD(true, 2); else GS_FWD(true, 3); }
   else { if (deg == 0) GS_FWD(false, 0); else if (deg == 1) GS_FWD(false, 1); else if (deg == 2) GS_FWD(false, 2); else GS_FWD(false, 3); }
 #undef GS_FWD
   return 0;
 }
 
-int gs_launch_preprocess_bwd(hipStream_t stream, int P, int D, int M, const float* means3D, const float* shs, const float* shs_rest,
-                             const float* scales, const float* rotations, int use_shs, int use_cov_precomp,
-                             const CamParams& cp, const int32_t* radii, const GsRec* recs, const float* cov3Ds, const uint8_t* clamped,
-                             const GsGrad* grads, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dshs_rest,
-                             float* dL_dcolors, float* dL_dopac, float* dL_dscales, float* dL_drots, float* dL_dcov3D,
-                             const GsPosed& posed_args, float* gate_flags, bool pose_only) {
+int gs_launch_preprocess_bwd(hipStream_t stream, const GsScene& sc, const CamParams& cp, const GsFrame& f, const GsGrad* grads,
+                             const GsGradOut& o, const GsPosed& posed_args, float* gate_flags, bool pose_only) {
+  const int P = sc.P, use_shs = sc.shs != nullptr, use_cov_precomp = sc.cov3D_precomp != nullptr;
   if (P <= 0) return 0;
   const bool posed = posed_args.pose != nullptr;
   const GsPosed pa = posed ? posed_args : GsPosed();
@@ -588,11 +584,11 @@ int gs_launch_preprocess_bwd(hipStream_t stream, int P, int D, int M, const floa
   const bool gi_on = posed && gate_flags;
   const int gi[4] = {gi_on ? GS_GATE_XYZ : -1, gi_on ? GS_GATE_ROT : -1, gi_on ? GS_GATE_SCALING : -1, gi_on ? GS_GATE_OPACITY : -1};
 #define GS_BWD(POSED, DEG, ...)                                                                                                         \
-  hipLaunchKernelGGL((k_preprocess_bwd<POSED, DEG, ##__VA_ARGS__>), dim3((P + 255) / 256), dim3(256), 0, stream, P, M, means3D, shs, shs_rest, scales, \
-                     rotations, use_shs, use_cov_precomp, cp, radii, recs, cov3Ds, clamped, grads, dL_dmeans3D, dL_dmeans2D, dL_dshs,  \
-                     dL_dshs_rest, dL_dcolors, dL_dopac, dL_dscales, dL_drots, dL_dcov3D, sh_gate, sh_rest_gate, pa, gate, gi[0],     \
-                     gi[1], gi[2], gi[3])
-  const int deg = use_shs ? D : 0;
+  hipLaunchKernelGGL((k_preprocess_bwd<POSED, DEG, ##__VA_ARGS__>), dim3((P + 255) / 256), dim3(256), 0, stream, P, sc.M, sc.means3D, sc.shs, sc.shs_rest, \
+                     sc.scales, sc.rotations, use_shs, use_cov_precomp, cp, f.radii, f.recs, f.cov3D, f.clamped, grads, o.means3D,    \
+                     o.means2D, o.shs, o.shs_rest, o.colors, o.opacities, o.scales, o.rotations, o.cov3D, sh_gate, sh_rest_gate, pa,   \
+                     gate, gi[0], gi[1], gi[2], gi[3])
+  const int deg = use_shs ? sc.D : 0;
   if (posed && pose_only) {
     if (deg == 0) GS_BWD(true, 0, true); else if (deg == 1) GS_BWD(true, 1, true); else if (deg == 2) GS_BWD(true, 2, true); else GS_BWD(true, 3, true);
   } else if (posed) { if (deg == 0) GS_BWD(true, 0); else if (deg == 1) GS_BWD(true, 1); else if (deg == 2) GS_BWD(true, 2); else GS_BWD(true, 3); }

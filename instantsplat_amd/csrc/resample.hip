@@ -157,7 +157,6 @@ int mi355gs_resample_rgb8(void* stream_, int N, int H, int W, int Hout, int Wout
                           int row0, int rows, void* scratch, uint8_t* rgb8, float* unit, float* normalized) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!rs_dim_ok(N) || !rs_image_ok(H, W) || !rs_image_ok(Hout, Wout) || !images || (!rgb8 && !unit && !normalized)) return MI355GS_EINVAL;
   if (x0 < 0 || y0 < 0 || w <= 0 || h <= 0 || w > Wout - x0 || h > Hout - y0) return MI355GS_EINVAL;
   const bool horizontal = kx != nullptr, vertical = ky != nullptr;

@@ -811,7 +811,6 @@ static inline dim3 plane_grid(int planes, int H, int W, int tw, int th) { return
 // in `scratch`.  `name`: the launch's range in a marker trace.
 static int launch_l1_ssim_fused(hipStream_t stream, int planes, int H, int W, const float* img1, const float* img2, float ks, float kl,
                                 float* dL_dimg1, void* scratch, const char* name) {
-  const int debug = 0;
   {
     GsProfScope prof(3, stream);
     GS_KRANGE(name);
@@ -840,7 +839,6 @@ int mi355gs_ssim_forward(void* stream_, int B, int C, int H, int W, const float*
                          float* dm_dsigma1_sq, float* dm_dsigma12, void* scratch, float* ssim_mean, float* l1_mean, int padding_valid) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!planes_ok(B, C, H, W) || !img1 || !img2 || !scratch) return MI355GS_EINVAL;
   const int crop = padding_valid ? HALO : 0;
   if (padding_valid && (l1_mean || H <= 2 * HALO || W <= 2 * HALO)) return MI355GS_EINVAL;
@@ -864,7 +862,6 @@ int mi355gs_ssim_backward(void* stream_, int B, int C, int H, int W, const float
                           const float* l1_grad_scale, float* dL_dimg1, int padding_valid) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!planes_ok(B, C, H, W) || !img1 || !img2 || !dL_dimg1) return MI355GS_EINVAL;
   if (ssim_grad_scale && (!dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12)) return MI355GS_EINVAL;
   const int crop = padding_valid ? HALO : 0;
@@ -883,7 +880,6 @@ size_t mi355gs_l1_scratch_bytes(int64_t n) { return gs_align((size_t)(n > 0 ? l1
 int mi355gs_l1_loss_forward(void* stream_, int64_t n, const float* a, const float* b, void* scratch, float* mean_out) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (n <= 0 || n > (int64_t)1 << 40 || !a || !b || !scratch || !mean_out) return MI355GS_EINVAL;
   GS_KRANGE("l1_partial");
   hipLaunchKernelGGL(k_l1_partial, dim3(l1_nblocks(n)), dim3(L1_THREADS), 0, stream, (long long)n, a, b, (float*)scratch);
@@ -898,7 +894,6 @@ int mi355gs_l1_loss_forward(void* stream_, int64_t n, const float* a, const floa
 int mi355gs_l1_loss_backward(void* stream_, int64_t n, const float* a, const float* b, const float* grad_scale, float* d_a) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (n <= 0 || n > (int64_t)1 << 40 || !a || !b || !grad_scale || !d_a) return MI355GS_EINVAL;
   GS_KRANGE("l1_bwd");
   hipLaunchKernelGGL(k_l1_bwd, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, (long long)n, a, b, grad_scale, (float)n, d_a);
@@ -912,7 +907,6 @@ int mi355gs_l1_ssim_loss_fused(void* stream_, int B, int C, int H, int W, const 
                                float lambda_dssim, float* ssim_mean, float* l1_mean, float* loss, float* dloss_dimg1) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!planes_ok(B, C, H, W) || !img1 || !img2 || !scratch || !loss || !dloss_dimg1) return MI355GS_EINVAL;
   const int rc = launch_l1_ssim_loss(stream, B * C, H, W, img1, img2, lambda_dssim, dloss_dimg1, scratch);
   if (rc != MI355GS_OK) return rc;
@@ -936,7 +930,6 @@ int mi355gs_l1_ssim_pair_backward(void* stream_, int64_t n, const float* img1, c
                                   const float* g_l1, float c_l1, const float* g_ssim, float c_ssim, float* d_img1) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (n <= 0 || n > (int64_t)1 << 40 || !img1 || !img2 || !d_img1) return MI355GS_EINVAL;
   if (c_ssim != 0.0f && !dssim_dimg1) return MI355GS_EINVAL;
   GS_KRANGE("loss_pair_bwd");
@@ -967,7 +960,6 @@ int mi355gs_loss_program_eval(void* stream_, int n_ops, const int32_t* ops, cons
                               const void* scratch, float* ssim_mean, float* l1_mean, float* out, float* host_out, float ticket) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!scratch || !l1_mean || !ssim_mean || !out) return MI355GS_EINVAL;
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ((uintptr_t)host_out & 7) != 0) return MI355GS_EINVAL;
   GsLossProgram p;
@@ -984,7 +976,6 @@ int mi355gs_loss_program_eval_grad(void* stream_, int n_ops, const int32_t* ops,
                                    const float* img1, const float* img2, const float* dssim_dimg1, float c_l1, float c_ssim, float* d_img1) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!scratch || !l1_mean || !ssim_mean || !out || !img1 || !img2 || !d_img1) return MI355GS_EINVAL;
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || ((uintptr_t)host_out & 7) != 0) return MI355GS_EINVAL;
   if (c_ssim != 0.0f && !dssim_dimg1) return MI355GS_EINVAL;
@@ -1015,7 +1006,6 @@ int mi355gs_metrics_rgb8(void* stream_, int N, int H, int W, const uint8_t* a, c
                          float* ssim_mean) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!metrics_rgb8_size_ok(N, H, W) || !a || !b || !scratch || !sq_sum || !ssim_mean) return MI355GS_EINVAL;
   const int tiles = ssim_nblocks(1, 1, H, W);
   float* part_ssim = (float*)scratch;

@@ -242,22 +242,21 @@ int mi355gs_tracker_run(void* handle, void* stream_, int sh_degree, const float*
   GS_RANGE();
   Tracker* t = (Tracker*)handle;
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!t || !t->degree_ok(sh_degree) || !gt_image || !projmatrix || !bg || !sched || !state) return MI355GS_EINVAL;
   if (num_iter <= 0 || first_iter < 0 || n_iters < 0 || first_iter > num_iter || n_iters > num_iter - first_iter) return MI355GS_EINVAL;
   if (n_iters == 0) return MI355GS_OK;
   int rc;
   if ((rc = ensure_consts(t, stream))) return rc;
   const int P = t->P, W = t->W, H = t->H;
-  const TilesLayout tl(W, H);
   const int n_pix = 3 * W * H, l1_blocks = l1_nblocks(W, H), rows = (P + 255) / 256;
   const GsScene scene = t->scene(sh_degree);
   const GsView view = t->view(projmatrix, tanfovx, tanfovy);
   const GsFrameBufs bufs = t->bufs(t->knobs, t->grad_scratch);
+  const GsFrame f(bufs, P, W, H);
   // the frame's accumulators (moment records, per-tile counters) are cleared by its first kernel, the projection
   GsPrologue pro;
   pro.grad_records = (float4*)t->grad_scratch; pro.n_vec = (size_t)P * 3;
-  pro.tile_counters = (uint32_t*)(t->tiles + tl.count); pro.n_counters = (int)((tl.start - tl.count) / 4);
+  pro.tile_counters = f.count; pro.n_counters = f.n_counters;
   GsFrameCtx cx;
   cx.prologue = &pro;
   cx.posed.pose = state + MI355GS_TRACKER_POSE;
@@ -273,7 +272,7 @@ int mi355gs_tracker_run(void* handle, void* stream_, int sh_degree, const float*
     if ((rc = gs_frame_backward(stream, scene, view, bufs, cx, bg, t->image, t->dL_dimg, GsGradOut(), false, 0))) return rc;
     GS_KRANGE("tracker_finish");
     hipLaunchKernelGGL(k_tracker_finish, dim3(1), dim3(1024), 0, stream, (const float*)t->pose_partial, rows,
-                       (const float*)t->loss_partial, l1_blocks, t->count(), (const uint32_t*)(t->tiles + tl.qmax), 4 * tl.T,
+                       (const float*)t->loss_partial, l1_blocks, t->count(), f.qmax, 4 * f.T,
                        (unsigned long long)t->capacity, (const float4*)sched, it, state,
                        pose_trace, loss_trace, grad_trace);
     GS_CHECK_LAUNCH("tracker_finish");

@@ -17,11 +17,6 @@
 #include <string.h>
 #include "common.h"
 
-int gs_loss_fused(hipStream_t, int, int, int, const float*, const float*, float, float*, void*);
-int gs_loss_fused_nblocks(int, int, int);
-int gs_launch_pose_finish_partials(hipStream_t, const float*, const float*, int, float*, float*, const float*, int, double, float, float*, int,
-                                   int);
-
 namespace {
 
 struct Trainer {
@@ -142,7 +137,7 @@ int mi355gs_posed_backward(void* stream_, int P, int D, int W, int H, const floa
   if (rc) return rc;
   GS_KRANGE("pose_finish");
   gs_launch_pose_finish_partials(stream, pose, pose_scratch, rows, d_pose, gate + GS_GATE_POSE, nullptr, 0, 0.0, 0.f, nullptr, pose_rows, pose_row);
-  GS_CHECK_LAUNCH("pose_finish");
+  GS_CHECK_LAUNCH_SYNC("pose_finish", stream, debug);
   return MI355GS_OK;
 }
 
@@ -189,7 +184,6 @@ int mi355gs_trainer_step(void* handle, void* stream_, int view, int sh_degree, c
   GS_RANGE();
   Trainer* t = (Trainer*)handle;
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   if (!t || view < 0 || view >= t->V || sh_degree < 0 || sh_degree > 3 || !gt_image || !projmatrix || !bg || !lr || !step || !loss_out || !num_rendered_out)
     return MI355GS_EINVAL;
   const int P = t->P, W = t->W, H = t->H;
@@ -201,13 +195,12 @@ int mi355gs_trainer_step(void* handle, void* stream_, int view, int sh_degree, c
     if (hipMemsetAsync(t->adam_live, 0, 16 * sizeof(uint32_t), stream) != hipSuccess) return MI355GS_ELAUNCH;
     t->consts_ready = true;
   }
+  const GsFrameBufs bufs = {t->geom, t->tiles, t->binning, t->capacity, t->radii, t->grad_scratch, t->knobs};
+  const GsFrame f(bufs, P, W, H);
   GsPrologue pro;  // the step's accumulators are cleared by its first kernel, the projection
-  {
-    const TilesLayout tl(W, H);
-    pro.grad_records = (float4*)t->grad_scratch; pro.n_vec = (size_t)P * 3;
-    pro.tile_counters = (uint32_t*)(t->tiles + tl.count); pro.n_counters = (int)((tl.start - tl.count) / 4);
-    pro.g_poses = t->g_poses; pro.n_pose = 7 * t->V; pro.pose_scratch = t->pose_scratch; pro.adam_scratch = t->adam_scratch;
-  }
+  pro.grad_records = (float4*)t->grad_scratch; pro.n_vec = (size_t)P * 3;
+  pro.tile_counters = f.count; pro.n_counters = f.n_counters;
+  pro.g_poses = t->g_poses; pro.n_pose = 7 * t->V; pro.pose_scratch = t->pose_scratch; pro.adam_scratch = t->adam_scratch;
   const float* pose = t->poses + 7 * (size_t)view;
   GsFrameCtx cx;
   cx.prologue = &pro;
@@ -217,7 +210,6 @@ int mi355gs_trainer_step(void* handle, void* stream_, int view, int sh_degree, c
   const int D = sh_degree;
   const GsScene scene = posed_scene(P, D, t->xyz, t->f_dc, t->f_rest, t->opacity, t->scaling, 1.0f, t->rotation);
   const GsView vw = {W, H, t->consts, projmatrix, t->consts + 16, tanfovx, tanfovy};
-  const GsFrameBufs bufs = {t->geom, t->tiles, t->binning, t->capacity, t->radii, t->grad_scratch, t->knobs};
   int rc;
   if ((rc = gs_frame_project(stream, scene, vw, bufs, cx, num_rendered_out, nullptr, 0))) return rc;
   if ((rc = gs_frame_render(stream, P, vw, bufs, bg, t->image, true, 0))) return rc;

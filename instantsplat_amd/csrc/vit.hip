@@ -263,7 +263,6 @@ struct VtDecScratch {
 
 
 int vt_layernorm(hipStream_t stream, int M, int D, const float* in, const float* wb, float* out) {
-  const int debug = 0;
   GS_KRANGE("vit_layernorm");
   hipLaunchKernelGGL(k_vit_layernorm, dim3((unsigned)((M + 3) / 4)), dim3(VT_T), 0, stream, M, D, in, wb, wb + D, out);
   GS_CHECK_LAUNCH("vit_layernorm");
@@ -272,7 +271,6 @@ int vt_layernorm(hipStream_t stream, int M, int D, const float* in, const float*
 
 int vt_attention(hipStream_t stream, int S, int N, int Wt, int P, int heads, const float* q, int ldq, const float* k, int ldk, const float* v,
                  int ldv, float* out, int ldo, const float* rope) {
-  const int debug = 0;
   GS_KRANGE("vit_attention");
   hipLaunchKernelGGL(k_vit_attention, dim3((unsigned)((N + VT_AQ - 1) / VT_AQ), (unsigned)heads, (unsigned)S), dim3(VT_T), 0, stream, N, N, Wt, P,
                      q, ldq, k, ldk, v, ldv, out, ldo, rope);
@@ -341,7 +339,6 @@ int mi355gs_vit_encode(void* stream_, const mi355gs_vit_config* cfg, const float
                        const float* images, void* scratch, float* feat) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const VtPlan p(cfg, Ht, Wt);
   if (!p.ok || V <= 0 || V > 256 || !weights || !rope || !images || !scratch || !feat) return MI355GS_EINVAL;
   if (!vt_aligned(weights, images, scratch, feat) || ((uintptr_t)rope & 3)) return MI355GS_EINVAL;
@@ -372,7 +369,6 @@ int mi355gs_vit_decode(void* stream_, const mi355gs_vit_config* cfg, const float
                        const int32_t* edges, const float* feat, void* scratch, float* const out1[4], float* const out2[4]) {
   GS_RANGE();
   hipStream_t stream = (hipStream_t)stream_;
-  const int debug = 0;
   const VtPlan p(cfg, Ht, Wt);
   if (!p.ok || V <= 0 || V > 256 || E <= 0 || E > 65535 || !weights || !rope || !edges || !feat || !scratch || !out1 || !out2) return MI355GS_EINVAL;
   if (!vt_aligned(weights, feat, scratch, nullptr) || ((uintptr_t)rope & 3)) return MI355GS_EINVAL;
